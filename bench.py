@@ -15,7 +15,13 @@ without WORLD_SIZE and with N > 1 this process starts N child ranks of
 itself (fresh interpreters, nothing here has touched the GPU yet) and exits
 with their status; rank 0 prints the line.
 
-The JSON line also carries:
+A plain run sets up, warms up, times the K epochs and prints the line
+(roofline and cpu_baseline null, no modes).  --dump-outputs DIR also writes
+the W and H tables of every block as they stand after the last timed epoch
+(DIR/W_<block>.npy, DIR/H_<block>.npy, in the run's precision): the data and
+the init stream are seeded, so two builds can be compared table for table.
+
+With --full the JSON line also carries:
   roofline     — the dominant kernel family (the most kernel time over a
                  second pass of the same K epochs right after the
                  uninstrumented timed region, every dispatch carrying HIP
@@ -68,6 +74,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp32")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the model tables after the last timed epoch as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-timing pass (roofline), the CPU baseline and the other modes; "
+                         "the options below narrow what --full adds")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--cpu-epochs", type=int, default=4)
     ap.add_argument("--cpu-single-epochs", type=int, default=1, help="one-thread oracle epochs (0: skip)")
@@ -101,12 +112,14 @@ def spawn_ranks(n):
 
 
 def run_newton(ds, prec, steps, warmup, k=32, self_side=True, world=1, rank=0, local=0, comm=None, allreduce=None,
-               pmc_tag="", snapshot=None):
+               pmc_tag="", snapshot=None, roofline=True, after_timed=None):
     """W warm-up epochs, K timed epochs (barrier + device sync on both sides,
-    max over ranks, no instrumentation), then the same K epochs again with
-    every dispatch carrying HIP events: the family with the most kernel
-    time over that pass is the dominant one, its average launch the
-    roofline's.  snapshot(g): called after the warm-up (CPU baseline)."""
+    max over ranks, no instrumentation), then (roofline=True, --full) the
+    same K epochs again with every dispatch carrying HIP events: the family
+    with the most kernel time over that pass is the dominant one, its
+    average launch the roofline's.  snapshot(g): called after the warm-up
+    (CPU baseline); after_timed(g): called right after the timed region
+    (--dump-outputs)."""
     ts = time.perf_counter()
     g = ocffm.problem_from_dataset(ds, precision=prec, with_test=False, device=local, rank=rank, nranks=world,
                                    comm=comm, allreduce=allreduce, k=k, self_side=self_side)
@@ -142,6 +155,16 @@ def run_newton(ds, prec, steps, warmup, k=32, self_side=True, world=1, rank=0, l
         dt = float(t.item())
     cg = g.cg_log()[cg0:]
     alg = g.alg_bytes()
+    if after_timed is not None:
+        after_timed(g)
+    # persistent column-Gram CG launches and the ones whose grid gave up on
+    # its barrier and finished per step (ocffm_problem_counter)
+    cgp = {"launches": g.counter("cgp_launches"), "recovered": g.counter("cgp_recovered")}
+    out = dict(dt=dt, roof=None, cg_per_epoch=round(cg.sum() / max(1, steps), 1),
+               setup_s={"create": round(t_create, 3), "init": round(t_init, 3)}, io_launches=None, cgp=cgp)
+    if not roofline:
+        g.close()
+        return out
     # kernel-timing pass: the same K epochs again, every dispatch carrying
     # start/stop HIP events on the solver stream
     g.reset_stats()
@@ -150,9 +173,7 @@ def run_newton(ds, prec, steps, warmup, k=32, self_side=True, world=1, rank=0, l
         g.one_epoch()
     barrier()
     ks = g.kernel_stats()
-    # persistent column-Gram CG launches and the ones whose grid gave up on
-    # its barrier and finished per step (ocffm_problem_counter)
-    cgp = {"launches": g.counter("cgp_launches"), "recovered": g.counter("cgp_recovered")}
+    out["cgp"] = {"launches": g.counter("cgp_launches"), "recovered": g.counter("cgp_recovered")}
     g.close()
 
     fams = {kk: v for kk, v in ks.items() if not kk.startswith("half(") and not kk.endswith(".noop")}
@@ -203,9 +224,9 @@ def run_newton(ds, prec, steps, warmup, k=32, self_side=True, world=1, rank=0, l
             pass
     # what ran, observed (not re-derived from the library's gate): the
     # item-owned CG steps' row pass appears in the kernel-timing pass
-    io_launches = int(ks.get("hs_cross_io", {}).get("launches", 0))
-    return dict(dt=dt, roof=roof, cg_per_epoch=round(cg.sum() / max(1, steps), 1),
-                setup_s={"create": round(t_create, 3), "init": round(t_init, 3)}, io_launches=io_launches, cgp=cgp)
+    out["io_launches"] = int(ks.get("hs_cross_io", {}).get("launches", 0))
+    out["roof"] = roof
+    return out
 
 
 T_START = time.perf_counter()
@@ -264,7 +285,7 @@ def main():
         # the compute cost of that path without any real exchange
         comm = ocffm.comm_id()
     snap = {}
-    want_cpu = rank == 0 and world == 1 and args.cpu_baseline == "auto"
+    want_cpu = args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto"
 
     def take(g):  # the GPU's tables after the warm-up: the CPU baseline starts there
         fu = int(ds.train.fid.max()) + 1
@@ -272,10 +293,18 @@ def main():
         snap["tables"] = {(w, b): g.get(w, b) for b in _blocks(fu, fv) for w in "WH"}
         snap["epoch"] = max(1, args.warmup) + 1
 
+    def dump(g):  # the tables a caller of one_epoch() reads back, after the last timed epoch
+        fu = int(ds.train.fid.max()) + 1
+        fv = int(ds.item.fid.max()) + 1
+        tables = {f"{w}_{b:02d}": g.get(w, b) for b in _blocks(fu, fv) for w in "WH"}  # every rank reads, rank 0 writes
+        if rank == 0:
+            dump_outputs(args.dump_outputs, tables, np.float32 if prec == ocffm.FP32 else np.float64)
+
     log(f"rank {rank}/{world}: kkbox-shape data ready, headline epochs")
     r = run_newton(ds, prec, args.steps, args.warmup, k=32, world=world, rank=rank, local=local, comm=comm,
                    allreduce=allreduce, pmc_tag="" if prec == ocffm.FP32 else "fp64_",
-                   snapshot=take if want_cpu else None)
+                   snapshot=take if want_cpu else None, roofline=args.full,
+                   after_timed=dump if args.dump_outputs else None)
     rows_total = ROWS_PER_GPU * world
     value = rows_total * args.steps / r["dt"]
 
@@ -284,7 +313,7 @@ def main():
         log("CPU baseline")
         cpu = cpu_baseline(ds, args.cpu_epochs, args.cpu_single_epochs, snap, r["cg_per_epoch"])
     modes = {}
-    if world == 1 and args.modes == "auto":
+    if args.full and world == 1 and args.modes == "auto":
         if prec == ocffm.FP32:
             modes["fp64"] = timed_mode(fp64_mode, ds, args)
         modes["kdd12"] = timed_mode(shape_mode, args, "kdd12")
@@ -309,8 +338,8 @@ def main():
                        "launcher": os.environ.get("OCFFM_BENCH_LAUNCHER", "torchrun" if world > 1 else "none"),
                        "allreduce": "gloo-host (rehearsal)" if rehearsal else ("rccl" if comm is not None else "none"),
                        # song-id item halves' CG steps item-owned: observed,
-                       # launches of their row pass in the kernel-timing pass
-                       "item_owned_cg": r["io_launches"] > 0,
+                       # launches of their row pass in the kernel-timing pass (--full; else null)
+                       "item_owned_cg": None if r["io_launches"] is None else r["io_launches"] > 0,
                        "item_owned_cg_launches": r["io_launches"],
                        "persistent_cg": r["cgp"],
                        "cg_iters_per_epoch": r["cg_per_epoch"]},
@@ -322,6 +351,26 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 48 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, arrays, dtype):
+    """DIR/<name>.npy of every array in `dtype`.  Past DUMP_LIMIT_BYTES in all,
+    every array keeps the same fraction of its elements: a fixed, seeded
+    sample (sorted flat indices, the same from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * np.dtype(dtype).itemsize
+    frac = min(1.0, DUMP_LIMIT_BYTES / max(1, total))
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        a = np.asarray(a).ravel()
+        if frac < 1.0:
+            keep = max(1, int(a.size * frac))
+            a = a[np.sort(np.random.default_rng(DUMP_SEED + i).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(dtype))
+    log(f"outputs written to {path}: {len(arrays)} arrays, {min(total, DUMP_LIMIT_BYTES) / 1e6:.1f} MB")
 
 
 def _blocks(fu, fv, self_side=True):

@@ -1,4 +1,5 @@
-"""Regenerate the nDCG known-answer fixtures (run in the build container only).
+"""Regenerate the nDCG known-answer fixtures, given the reference's tool directory:
+    python tests/golden/make_ndcg_kat.py <reference checkout>/script/nDCG_degub_tool
 
 The reference's only known-answer test is ``script/nDCG_degub_tool``: a
 debug build forces the item scores to z_j = n - j and prints nDCG per test
@@ -29,7 +30,9 @@ import subprocess
 import sys
 import tempfile
 
-REF = "/root/reference/script/nDCG_degub_tool"
+if len(sys.argv) != 2:
+    sys.exit("usage: make_ndcg_kat.py <reference checkout>/script/nDCG_degub_tool")
+REF = sys.argv[1]
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "ndcg_kat")
 TOP_K = (5, 10, 20, 40, 80)

@@ -3,7 +3,7 @@
 // by tests/test_sanitize.py over the parser's edge-case inputs.  It drives
 // the same calls as the C ABI (ocffm_data_read: parse_rows + build;
 // ocffm_data_trans_y; the data getters: split_host), restating ImpData
-// (/root/reference/ffm.cpp:80-294), and prints a digest of what was parsed.
+// (the reference's ffm.cpp:80-294), and prints a digest of what was parsed.
 //
 //   parse_driver TRAIN ITEM [TEST]
 // exit 0 ok, 3 invalid_argument (a malformed label, as stoi throws in the

@@ -5,7 +5,8 @@ The driver's scale command is `python bench.py --gpus N`: without torchrun's
 environment the script must start N ranks itself, and rank 0 must report
 n_gpus = N with every rank accounted for.  Under torchrun (WORLD_SIZE set)
 it must not spawn again, and a --gpus that disagrees with WORLD_SIZE is an
-error rather than a mislabelled line.
+error rather than a mislabelled line.  Also --dump-outputs' writer on
+made-up arrays.
 """
 import json
 import os
@@ -50,6 +51,36 @@ def test_torchrun_world_is_used():
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert lines == [{"n_gpus": 2, "ranks_seen": 2, "launcher": "torchrun"}]
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: every array whole below the size limit; past it the
+    same seeded sample of each array's elements from run to run, within the limit."""
+    import importlib.util
+
+    import numpy as np
+    monkeypatch.setattr(sys, "argv", [BENCH])
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    arrays = {"W_00": rng.standard_normal(1000), "H_00": rng.standard_normal(3001), "W_01": np.arange(7.0)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays, np.float64)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4008 * 4 // 4)  # a quarter of the 4008 float32 elements
+    bench.dump_outputs(str(tmp_path / "a"), arrays, np.float32)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, np.float32)
+    kept = 0
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, np.load(tmp_path / "b" / (name + ".npy")))
+        assert got.size == max(1, a.size // 4)
+        pos = np.searchsorted(np.sort(a.astype(np.float32)), got)  # elements of a, each at most once
+        assert np.array_equal(np.sort(a.astype(np.float32))[pos], got) and np.unique(pos).size == got.size
+        kept += got.nbytes
+    assert kept <= 4008
 
 
 def test_gpus_disagreeing_with_world_is_an_error():

@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, '/root/repo/one-class-ffm_amd')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'one-class-ffm_amd'))
 import ocffm, synth
 for n in (100000, 25000, 12500):
     ds = synth.kkbox(n=n)
