@@ -171,6 +171,46 @@ int ocffm_problem_validate_forced(ocffm_problem *p, ocffm_metrics *out, double *
  * test set). */
 int ocffm_problem_test_rows(ocffm_problem *p, uint64_t *m);
 
+/* Top-N recommendation (no reference counterpart: the reference only scores
+ * inside validate).  Top-N items for rows [row0, row0+rows) of X under the
+ * current model.
+ * X: user rows in the train set's field space (read with the train Ds, as a
+ * test file is).  items: rows x topn, row-major.  scores (may be NULL): the
+ * same shape, the model's prediction  a_i + b_j + sum_c <P_c[i], Q_c[j]>
+ * (pred_z, ffm.cpp:915-923, plus the row's own side term a_i, which is added
+ * before the selection so that the order below is the order of the returned
+ * values).  Order: score descending, equal scores by ascending item index.
+ * Does not change the solver state.
+ *  - Candidates: every item row j < n of V.  With OCFFM_REC_EXCLUDE_LABELS in
+ *    flags, the row's own labels in X are excluded (labels >= n are ignored,
+ *    and so is the flag when X has no labels).
+ *  - Cold rows: a row with no kept feature node is scored as validate scores
+ *    it (ffm.cpp:975-977): its candidates are j < npop (the train set's
+ *    max label + 1), its scores the train popularity values; the same
+ *    ordering and exclusion rules hold.
+ *  - Short rows: a row with fewer than topn candidates has OCFFM_REC_NONE and
+ *    a score of -inf in the remaining slots.
+ *  - Arithmetic: the problem's precision (fp32 tables and accumulation in
+ *    OCFFM_FP32, fp64 in OCFFM_FP64), returned as fp64.
+ *  - Reproducibility: a row's result is the same bit for bit between calls
+ *    and does not depend on its position in the call nor on how the call was
+ *    chunked or the items sliced (OCFFM_REC_ROWS, OCFFM_REC_SLICES): the
+ *    selection is on the total order (score, item index).
+ *  - Errors: OCFFM_E_STATE before init / load_binary; OCFFM_E_ARG for
+ *    topn == 0, topn > OCFFM_REC_MAX_TOPN, row0 + rows > X.m, NULL items, or
+ *    an X with more fields than the train set's user side; OCFFM_E_DATA for
+ *    a node of X with idx >= Ds[fid].  rows == 0 is OCFFM_OK.
+ *  - Sharded problems: the owned tables are made whole first, as in
+ *    validate; X is not sharded, each rank scores the rows it passes.  This
+ *    has only been run on one rank.
+ * The launches are the kernel family "recommend" of the statistics below;
+ * the counter "rec_setup_us" holds the last call's host-side set-up time. */
+#define OCFFM_REC_MAX_TOPN 128
+#define OCFFM_REC_EXCLUDE_LABELS 1u /* flags bit: drop each row's own labels from its candidates */
+#define OCFFM_REC_NONE 0xffffffffu  /* item id of an unfilled slot */
+int ocffm_problem_recommend(ocffm_problem *p, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
+                            uint32_t flags, uint32_t *items, double *scores);
+
 /* print_epoch_info (ffm.cpp:1130-1145) of the last validation, and the
  * header of init_va (ffm.cpp:901-912), to stdout. */
 int ocffm_print_header(void);

@@ -341,6 +341,8 @@ struct ProblemBase {
   virtual void cache_sasb() = 0;
   virtual void validate(ocffm_metrics *m, bool forced = false, double *per_row_ndcg = nullptr, uint64_t cap = 0) = 0;
   virtual uint64_t test_rows() const = 0;
+  virtual void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags,
+                         uint32_t *items, double *scores) = 0;
   virtual uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) = 0;
   virtual void set(char what, uint32_t b12, const double *in, uint64_t len) = 0;
   virtual void grad(uint32_t f1, uint32_t f2, int half, double *out) = 0;
@@ -395,6 +397,8 @@ template <typename real> class Problem final : public ProblemBase {
     if (const char *e = std::getenv("OCFFM_FEAT_BLOCKS")) feat_blocks_ = (unsigned)std::max(1, std::atoi(e));
     if (const char *e = std::getenv("OCFFM_FUSE")) fuse_ = std::atoi(e) != 0;  // id-field side Hv rows finalise their column
     if (const char *e = std::getenv("OCFFM_NO_OWNED")) no_owned_ = std::atoi(e) != 0;  // all-reduce every field
+    if (const char *e = std::getenv("OCFFM_REC_SLICES")) rec_slices_ = (unsigned)std::clamp(std::atoi(e), 1, 256);
+    if (const char *e = std::getenv("OCFFM_REC_ROWS")) rec_rows_ = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     // shard users contiguously
     u0_ = U.m * (uint64_t)comm_.rank / (uint64_t)comm_.nranks;
     u1_ = U.m * (uint64_t)(comm_.rank + 1) / (uint64_t)comm_.nranks;
@@ -1010,6 +1014,149 @@ template <typename real> class Problem final : public ProblemBase {
       out->prec[s] = tot[1 + s] / (mt_glob * cuts[s]);
       out->ndcg[s] = tot[6 + s] / mt_glob;
     }
+  }
+
+  // ---------------------------------------------------- recommendation
+  // Top-N items of rows [row0, row0 + rows) of X (ocffm.h
+  // ocffm_problem_recommend).  The rows' user-side layout is built as a test
+  // file's is (build_fields with the train Ds) and projected through utx;
+  // the item side is the resident Q_ / V_.bias.  The rows are scored in
+  // chunks: scratch is chunk x slices x topn partial entries, never rows x n.
+  void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
+                 double *scores) override {
+    need_init();
+    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
+    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
+    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    if (X.f > fu_) throw Error(OCFFM_E_ARG, "X has more fields than the train set's user side");
+    if (rows == 0) return;
+    const uint64_t r1 = row0 + rows;
+    for (uint64_t p = X.raw.xptr[row0]; p < X.raw.xptr[r1]; p++)
+      if (X.raw.fid[p] >= fu_ || X.raw.idx[p] >= U_.Ds[X.raw.fid[p]])
+        throw Error(OCFFM_E_DATA, "X has a node with idx >= Ds[fid] (read it with the train Ds)");
+    sync_owned();
+    sync();
+    const auto th0 = std::chrono::steady_clock::now();
+    // the rows' layout and projections
+    DevSide<real> Xs;
+    Xs.R = Xs.R_glob = rows;
+    Xs.row0 = row0;
+    {
+      dev::Builder B(stream_);
+      build_fields(Xs, X, row0, r1, U_.Ds, B);
+      B.sync();
+    }
+    std::vector<DevBuf<real>> Px(std::max<uint32_t>(C_, 1));
+    std::vector<real *> tl(std::max<uint32_t>(C_, 1), nullptr);
+    for (uint32_t c = 0, f1 = 0; f1 < fu_; f1++)
+      for (uint32_t f2 = fu_; f2 < f_; f2++, c++) {
+        Px[c].alloc(rows * kp_, false);
+        utx(Xs, f1, W_[block_index(f1, f2, f_)].p, Px[c].p);
+        tl[c] = Px[c].p;
+      }
+    DevBuf<real *> pt;
+    pt.upload(tl);
+    DevBuf<real> ax;  // a_i (zero without the side blocks)
+    ax.alloc(rows);
+    if (prm_.self_side) {
+      DevBuf<real> p1, p2;
+      p1.alloc(rows * kp_, false);
+      p2.alloc(rows * kp_, false);
+      for (uint32_t f1 = 0; f1 < fu_; f1++)
+        for (uint32_t f2 = f1; f2 < fu_; f2++) {
+          const uint32_t b12 = block_index(f1, f2, f_);
+          utx(Xs, f1, W_[b12].p, p1.p);
+          utx(Xs, f2, H_[b12].p, p2.p);
+          rowdot_add(rows, p1.p, p2.p, ax.p);
+        }
+      sync();  // (p1 / p2 are freed here)
+    }
+    std::vector<uint8_t> cold(rows);
+    for (uint64_t i = 0; i < rows; i++) cold[i] = X.nnx[row0 + i] == 0;
+    DevBuf<uint8_t> dcold;
+    dcold.upload(cold);
+    // each row's labels < n, sorted and distinct
+    const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
+    std::vector<int64_t> lptr(rows + 1, 0);
+    std::vector<uint32_t> lcol;
+    if (excl)
+      for (uint64_t i = 0; i < rows; i++) {
+        const size_t b = lcol.size();
+        for (uint64_t p = X.yptr[row0 + i]; p < X.yptr[row0 + i + 1]; p++)
+          if (X.ycol[p] < n_) lcol.push_back((uint32_t)X.ycol[p]);
+        std::sort(lcol.begin() + b, lcol.end());
+        lcol.erase(std::unique(lcol.begin() + b, lcol.end()), lcol.end());
+        lptr[i + 1] = (int64_t)lcol.size();
+      }
+    if (lcol.empty()) lcol.push_back(0);
+    DevBuf<int64_t> dlptr;
+    DevBuf<uint32_t> dlcol;
+    dlptr.upload(lptr);
+    dlcol.upload(lcol);
+    // chunking and slicing
+    const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
+    const uint64_t rt = (chunk + REC_RT - 1) / REC_RT;
+    uint64_t S = rec_slices_;
+    if (!S) {
+      // one resident wave of blocks: every slice costs each row its own
+      // list warm-up (~topn inserts), so as few slices as fill the machine;
+      // at least 4 item tiles per slice
+      unsigned slots = 2 * ncu_;
+      with_kp(kp_, [&](auto K) { slots = resident(k_rec_topn<real, decltype(K)::value>, 0); });
+      S = std::max<uint64_t>(1, slots / rt);
+      S = std::min<uint64_t>(S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
+      S = std::clamp<uint64_t>(S, 1, 64);
+    }
+    const uint64_t per = ((n_ + S - 1) / S + REC_IT - 1) / REC_IT * REC_IT;
+    DevBuf<double> part_v, out_v;
+    DevBuf<uint32_t> part_j, out_j;
+    part_v.alloc(chunk * S * topn, false);
+    part_j.alloc(chunk * S * topn, false);
+    out_v.alloc(chunk * topn, false);
+    out_j.alloc(chunk * topn, false);
+    sync();
+    counters["rec_setup_us"] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
+    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
+      const uint64_t cr = std::min(chunk, rows - c0);
+      RecArgs<real> g{};
+      g.R = cr;
+      g.p0 = c0;
+      g.n = n_;
+      g.npop = std::min<uint64_t>(npop_, n_);
+      g.per = per;
+      g.C = (int)C_;
+      g.S = (uint32_t)S;
+      g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
+      g.topn = (int)topn;
+      g.exclude = excl ? 1 : 0;
+      g.P = pt.p;
+      g.Q = tabs_.p + C_;
+      g.a = ax.p + c0;
+      g.b = V_.bias.p;
+      g.cold = dcold.p + c0;
+      g.popular = popular_.p;
+      g.lptr = dlptr.p + c0;
+      g.lcol = dlcol.p;
+      g.part_v = part_v.p;
+      g.part_j = part_j.p;
+      const double depth = (double)C_ * kp_;
+      const double bytes = ((double)cr + (double)n_) * depth * sizeof(real) + (double)n_ * sizeof(real) +
+                           (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
+      prof_launch("recommend", bytes, [&] {
+        with_kp(kp_, [&](auto K) {
+          constexpr int KP = decltype(K)::value;
+          launch(k_rec_topn<real, KP>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
+        });
+        launch(k_rec_merge, (unsigned)cr, BLOCK, 0, cr, (int)S, (int)topn, (const double *)part_v.p,
+               (const uint32_t *)part_j.p, out_j.p, out_v.p);
+      }, 2.0 * (double)cr * (double)n_ * depth);
+      HIPCHK(hipMemcpyAsync(items + c0 * topn, out_j.p, cr * topn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+      if (scores)
+        HIPCHK(hipMemcpyAsync(scores + c0 * topn, out_v.p, cr * topn * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      sync();
+    }
+    flush_prof();
   }
 
   // ----------------------------------------------------------- access
@@ -3926,6 +4073,8 @@ template <typename real> class Problem final : public ProblemBase {
   hipEvent_t arm_a_ = nullptr, arm_b_ = nullptr;
   bool arm_first_ = false;
   DevSide<real> U_, V_, T_;
+  unsigned rec_slices_ = 0;  // OCFFM_REC_SLICES (0: from n, the rows and the CU count)
+  uint64_t rec_rows_ = 0;    // OCFFM_REC_ROWS (0: 4096 rows per chunk)
   std::vector<Block> blocks_;
   std::vector<DevBuf<real>> W_, H_, P_, Q_;
   DevBuf<real> acc_, G_, S_, Vd_, Rv_, Hv_, h_, M_, wpart_;
@@ -4210,6 +4359,10 @@ int ocffm_problem_validate_forced(ocffm_problem *prob, ocffm_metrics *m, double 
 }
 int ocffm_problem_test_rows(ocffm_problem *prob, uint64_t *m) {
   PROB_CALL(if (!m) throw Error(OCFFM_E_ARG, "null output"); *m = prob->p->test_rows());
+}
+int ocffm_problem_recommend(ocffm_problem *prob, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
+                            uint32_t flags, uint32_t *items, double *scores) {
+  PROB_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); prob->p->recommend(X->d, row0, rows, topn, flags, items, scores));
 }
 int ocffm_problem_save_binary(ocffm_problem *prob, const char *path) { PROB_CALL(prob->p->save_binary(path)); }
 int ocffm_problem_load_binary(ocffm_problem *prob, const char *path) { PROB_CALL(prob->p->load_binary(path)); }

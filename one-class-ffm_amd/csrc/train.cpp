@@ -7,7 +7,10 @@
 //   -c threads  -k rank  --ns  --freq
 // Build-only options (the reference would take them for the item file):
 //   --fp32 / --fp64 (default fp64, the reference's arithmetic type),
-//   --device N.
+//   --device N;
+//   --recommend <file> --topn <n> --rec-out <path> [--rec-unseen]: after the
+//   solve (and any model save) the top-n items of every row of <file> (read
+//   like a -p file) go to <path>, one line of item:score tokens per row.
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -16,6 +19,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/ocffm.h"
 
@@ -34,7 +38,11 @@ static std::string usage() {
          "--ns: no self-side field pairs\n"
          "--freq: enable freq-aware lambda\n"
          "--fp32 | --fp64: device arithmetic (default fp64)\n"
-         "--device <n>: HIP device ordinal\n";
+         "--device <n>: HIP device ordinal\n"
+         "--recommend <path>: after training, recommend items for every row of this file (read like -p)\n"
+         "--topn <n>: items per row, 1..128 (default 10)\n"
+         "--rec-out <path>: where the recommendations go (one line of item:score per row)\n"
+         "--rec-unseen: leave out each row's own labels\n";
 }
 
 // train.cpp:22-32: at least one digit somewhere in the token.
@@ -56,7 +64,9 @@ static void check(int st) {
 int main(int argc, char **argv) {
   ocffm_param prm;
   ocffm_param_default(&prm);
-  std::string te_path, model_path;
+  std::string te_path, model_path, rec_path, rec_out;
+  long topn = 10;
+  bool rec_unseen = false;
   try {
     if (argc == 1) throw std::invalid_argument(usage());
     int i = 1;
@@ -81,8 +91,14 @@ int main(int argc, char **argv) {
       else if (a == "--fp32") prm.precision = OCFFM_FP32;
       else if (a == "--fp64") prm.precision = OCFFM_FP64;
       else if (a == "--device") prm.device = std::atoi(value(true, "need a device ordinal after --device"));
+      else if (a == "--recommend") rec_path = value(false, "need to specify path after --recommend");
+      else if (a == "--rec-out") rec_out = value(false, "need to specify path after --rec-out");
+      else if (a == "--topn") topn = std::atol(value(true, "need to specify the number of items after --topn"));
+      else if (a == "--rec-unseen") rec_unseen = true;
       else break;
     }
+    if (!rec_path.empty() && rec_out.empty()) throw std::invalid_argument("--recommend needs --rec-out <path>");
+    if (topn < 1 || topn > OCFFM_REC_MAX_TOPN) throw std::invalid_argument("--topn must be in 1..128");
     if (i >= argc) throw std::invalid_argument("training data not specified");
     if (i + 1 >= argc) throw std::invalid_argument("training data not specified");
     const std::string item_path = argv[i], tr_path = argv[i + 1];
@@ -122,6 +138,30 @@ int main(int argc, char **argv) {
     phase("solve");
     if (!model_path.empty()) check(ocffm_problem_save_model(prob, model_path.c_str()));
     phase("save");
+    if (!rec_path.empty()) {
+      ocffm_data_info info;
+      check(ocffm_data_get_info(U, &info));
+      std::vector<std::uint64_t> ds(info.f ? info.f : 1);
+      check(ocffm_data_get_ds(U, ds.data()));
+      ocffm_data *X = nullptr;
+      check(ocffm_data_read(rec_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
+      ocffm_data_info xi;
+      check(ocffm_data_get_info(X, &xi));
+      std::vector<uint32_t> items(xi.m * (size_t)topn + 1);
+      std::vector<double> scores(xi.m * (size_t)topn + 1);
+      check(ocffm_problem_recommend(prob, X, 0, xi.m, (uint32_t)topn, rec_unseen ? OCFFM_REC_EXCLUDE_LABELS : 0u,
+                                    items.data(), scores.data()));
+      std::FILE *fp = std::fopen(rec_out.c_str(), "w");
+      if (!fp) throw Fail(OCFFM_E_IO, "cannot write " + rec_out);
+      for (std::uint64_t i = 0; i < xi.m; i++) {
+        for (long t = 0; t < topn && items[i * topn + t] != OCFFM_REC_NONE; t++)
+          std::fprintf(fp, t ? " %u:%.17g" : "%u:%.17g", items[i * topn + t], scores[i * topn + t]);
+        std::fputc('\n', fp);
+      }
+      if (std::fclose(fp) != 0) throw Fail(OCFFM_E_IO, "write failed: " + rec_out);
+      ocffm_data_free(X);
+      phase("recommend");
+    }
     ocffm_problem_destroy(prob);
     ocffm_data_free(U);
     ocffm_data_free(V);

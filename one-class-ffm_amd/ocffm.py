@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("OCFFM_LIB") or os.path.join(HERE, "libocffm.so")  # o
 
 OK, E_ARG, E_IO, E_DATA, E_HIP, E_COMM, E_STATE = range(7)
 FP64, FP32 = 64, 32
+REC_MAX_TOPN, REC_EXCLUDE_LABELS, REC_NONE = 128, 1, 0xFFFFFFFF
 COMM_ID_BYTES = 128
 
 
@@ -65,6 +66,7 @@ EXPORTS = [
     "ocffm_problem_validate", "ocffm_print_header", "ocffm_print_epoch", "ocffm_problem_get",
     "ocffm_problem_set", "ocffm_problem_grad", "ocffm_problem_hv", "ocffm_problem_save_model",
     "ocffm_problem_validate_forced", "ocffm_problem_test_rows", "ocffm_problem_save_binary", "ocffm_problem_load_binary",
+    "ocffm_problem_recommend",
     "ocffm_problem_cg_log", "ocffm_problem_set_profiling", "ocffm_problem_set_profile_filter",
     "ocffm_problem_kernel_stats",
     "ocffm_problem_reset_stats", "ocffm_problem_alg_bytes", "ocffm_problem_counter", "ocffm_problem_sync",
@@ -115,6 +117,7 @@ def lib():
     L.ocffm_problem_save_model.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_validate_forced.argtypes = [vp, C.POINTER(_Metrics), vp, u64]
     L.ocffm_problem_test_rows.argtypes = [vp, C.POINTER(u64)]
+    L.ocffm_problem_recommend.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp]
     L.ocffm_problem_save_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_load_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_cg_log.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
@@ -430,6 +433,23 @@ class ImpProblem:
         rows = np.zeros(max(1, mt) * 5, dtype=np.float64)
         _check(lib().ocffm_problem_validate_forced(self.h, C.byref(m), _ptr(rows), rows.size))
         return dict(loss=m.loss, prec=np.array(m.prec[:]), ndcg=np.array(m.ndcg[:])), rows[:mt * 5].reshape(mt, 5)
+
+    def recommend(self, X: ImpData, topn: int = 10, exclude_labels: bool = False, row0: int = 0,
+                  rows: Optional[int] = None):
+        """Top-``topn`` items of rows [row0, row0 + rows) of ``X`` (default: to its
+        end) under the current model (include/ocffm.h ocffm_problem_recommend):
+        ``(items uint32 [rows, topn], scores float64 [rows, topn])``, score
+        descending, equal scores by ascending item; unfilled slots hold
+        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels."""
+        if rows is None:
+            rows = max(0, int(X.info["m"]) - row0)
+        shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
+        items = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        _check(lib().ocffm_problem_recommend(self.h, X.h, row0, rows, topn,
+                                             REC_EXCLUDE_LABELS if exclude_labels else 0,
+                                             items.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
+        return items, scores
 
     def save_binary(self, path: str) -> None:
         _check(lib().ocffm_problem_save_binary(self.h, path.encode()))
