@@ -211,6 +211,82 @@ int ocffm_problem_test_rows(ocffm_problem *p, uint64_t *m);
 int ocffm_problem_recommend(ocffm_problem *p, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
                             uint32_t flags, uint32_t *items, double *scores);
 
+/* Exact label ranks (no reference counterpart).  For every label of X, its
+ * rank among the candidates of its row under the current model: the 0-based
+ * number of candidates that come before it in the order of
+ * ocffm_problem_recommend (score descending, equal scores by ascending item
+ * index; ties are thus broken by item index).  The other labels of the row
+ * count as candidates too.
+ * X: labelled user rows in the train set's field space (read with the train
+ * Ds).  ranks, scores (may be NULL): one entry per label of X in
+ * ocffm_data_get_labels order (info.nnz_y entries); a score is the value
+ * ocffm_problem_recommend returns for that (row, item), bit for bit.
+ * ncand (may be NULL): the candidate count of each of the X.m rows.
+ * Does not change the solver state.
+ *  - Candidates of row i: every item j < n of V; for a cold row (no kept
+ *    feature node) j < npop, scored by train popularity as in recommend.
+ *    With seen != NULL the labels of seen's row i are removed (seen.m must
+ *    equal X.m; its labels >= n are ignored).
+ *  - Labels that are not candidates (>= n, >= npop on a cold row, or present
+ *    in seen) get OCFFM_RANK_NONE and a score of -inf.
+ *  - Duplicate labels: every copy gets the same rank and score.
+ *  - Arithmetic and reproducibility: as ocffm_problem_recommend.  A label's
+ *    rank and score are the same bit for bit between calls and do not depend
+ *    on the row's position in X nor on OCFFM_REC_ROWS / OCFFM_REC_SLICES,
+ *    which chunk and slice this call as well.  No rows x n array is built.
+ *  - Errors: OCFFM_E_STATE before init / load_binary; OCFFM_E_ARG for NULL
+ *    ranks, an X without labels, seen.m != X.m, or an X with more fields than
+ *    the train set's user side; OCFFM_E_DATA for a node of X with
+ *    idx >= Ds[fid].  X.m == 0 is OCFFM_OK.
+ *  - Sharded problems: the owned tables are made whole first, as in
+ *    validate; X is not sharded, each rank ranks the rows it passes.  This
+ *    has only been run on one rank.
+ * The launches are the kernel family "evaluate" of the statistics below; the
+ * counter "eval_setup_us" holds the last call's host-side set-up time. */
+#define OCFFM_RANK_NONE 0xffffffffu
+int ocffm_problem_label_ranks(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
+                              double *scores, uint32_t *ncand);
+
+/* Ranking metrics from label ranks.  ocffm_eval_from_ranks is pure host code
+ * (no GPU, no problem): yptr holds the m + 1 label offsets of the rows,
+ * ranks / scores (may be NULL: loss 0) / ncand the outputs of
+ * ocffm_problem_label_ranks.  Sums are taken in fp64 in row order.
+ * A row's ranked labels are its distinct labels with a rank other than
+ * OCFFM_RANK_NONE: P of them, ranks r_1 < ... < r_P (copies of a label share
+ * a rank and count once).  rows_used counts the rows with P >= 1; every mean
+ * below is over those rows, the others are skipped; with rows_used == 0
+ * every metric is 0.  labels = yptr[m], labels_ranked = the sum of P.
+ * For a cut c the hits are the labels with r < c:
+ *   prec   = hits / c  (the divisor is c even with fewer candidates, as in
+ *            the reference's prec_k)
+ *   recall = hits / P
+ *   ndcg   = sum_hits 1/log2(r + 2)  /  sum_{t < min(c, P)} 1/log2(t + 2)
+ *   map    = (1 / min(c, P)) sum_{hits t} t / (r_t + 1), t the label's
+ *            1-based index among the row's ranked labels
+ *   hit    = 1 if hits > 0, else 0
+ * and without a cut:
+ *   mrr    = 1 / (r_1 + 1)
+ *   auc    = 1 - sum_t (r_t - (t - 1)) / (P (ncand - P)): the fraction of
+ *            (label, other candidate) pairs the model orders correctly, ties
+ *            broken by item index; a row with ncand == P is left out of this
+ *            mean (which is over the remaining rows)
+ *   loss   = sqrt(sum over ranked labels of (1 - s)^2 / rows_used), the
+ *            ploss of validate.
+ * cuts: 1 <= ncut <= OCFFM_EVAL_MAX_CUTS values >= 1, strictly increasing;
+ * otherwise OCFFM_E_ARG, as for a NULL yptr / ranks / ncand / cuts / out.
+ * ocffm_problem_evaluate is ocffm_problem_label_ranks followed by
+ * ocffm_eval_from_ranks, with the errors of both. */
+#define OCFFM_EVAL_MAX_CUTS 8
+typedef struct ocffm_eval {
+  uint64_t rows, rows_used, labels, labels_ranked;
+  uint32_t ncut, cuts[8];
+  double loss, mrr, auc, prec[8], recall[8], ndcg[8], map[8], hit[8];
+} ocffm_eval;
+int ocffm_eval_from_ranks(uint64_t m, const uint64_t *yptr, const uint32_t *ranks, const double *scores,
+                          const uint32_t *ncand, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out);
+int ocffm_problem_evaluate(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
+                           uint32_t ncut, ocffm_eval *out);
+
 /* print_epoch_info (ffm.cpp:1130-1145) of the last validation, and the
  * header of init_va (ffm.cpp:901-912), to stdout. */
 int ocffm_print_header(void);

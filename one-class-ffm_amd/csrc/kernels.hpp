@@ -4325,4 +4325,264 @@ static __global__ __launch_bounds__(BLOCK) void k_rec_merge(uint64_t R, int S, i
   }
 }
 
+// ------------------------------------------------- ranking evaluation ---
+// Exact rank of every label among its row's candidates
+// (ocffm_problem_label_ranks): the label's own score is computed first, then
+// one sweep over all items counts, per label, the candidates that come before
+// it.  No rows x n array and no top-N list exists.
+//
+// k_eval_label_scores: a wave takes 16 (row, item) pairs; lane l holds the
+// operands of pair l & 15 on both sides of the MFMA and runs k_rec_topn's
+// chain (chunks of 16 depth elements in order, then (acc + b_j) + a_i), so the
+// diagonal of the 16 x 16 product holds each pair's score with the bits the
+// sweep gives it: an output element depends only on its own row and item.
+template <typename real, int KP>
+__global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, const real *const *__restrict__ P,
+                                                             const real *const *__restrict__ Q,
+                                                             const real *__restrict__ a, const real *__restrict__ b,
+                                                             const uint8_t *__restrict__ cold,
+                                                             const double *__restrict__ popular,
+                                                             const uint32_t *__restrict__ lrow,
+                                                             const uint32_t *__restrict__ litem,
+                                                             double *__restrict__ out) {
+  using M = RecMma<real>;
+  using V = typename M::V;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int m = lane & 15, q = lane >> 4;
+  const uint64_t e = ((uint64_t)blockIdx.x * (BLOCK / 64) + w) * 16 + m;
+  const bool have = e < L;
+  const uint64_t row = have ? lrow[e] : 0, item = have ? litem[e] : 0;
+  const int depth = C * KP, nch = (depth + 15) / 16;
+  const V zero = {(real)0, (real)0, (real)0, (real)0};
+  V acc = zero;
+  for (int c = 0; c < nch; c++) {
+    const int d = 16 * c + 4 * q;
+    const bool in = d < depth && have;
+    const int tb = d < depth ? d / KP : 0, el = d % KP;
+    const V av = in ? M::ld(P[tb] + row * KP + el) : zero;
+    const V bv = in ? M::ld(Q[tb] + item * KP + el) : zero;
+#pragma unroll
+    for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
+  }
+  if (!have) return;
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+    if (M::drow(q, r) == m) out[e] = cold[row] ? popular[item] : (double)((acc[r] + b[item]) + a[row]);
+}
+
+// k_eval_count: k_rec_topn's tiling and score chain without the lists.  A
+// candidate (s_ij, j) of row i that is inside the slice, a candidate at all
+// (j < n; cold rows: j < npop, score popular[j]) and not in the row's sorted
+// seen list is located among the row's labels, which are sorted by the same
+// order (score descending, item ascending): it adds one to the counter of the
+// first label it ranks strictly before; one compare against the row's last
+// label drops a candidate that ranks before none.  The prefix sum of a row's
+// counters is then each label's rank.  The labels of a row with at most
+// EV_LC of them are searched in LDS.  Counters of a row with at most
+// EV_CAP labels are kept in LDS and added to the global ones once per block;
+// a longer row adds to the global counters directly.  Adds from one tile to
+// one counter are merged into one.  Integer adds commute: the result does
+// not depend on slicing or scheduling.
+constexpr int EV_CAP = 128;
+constexpr int EV_LC = 16;  // labels of a row that are also searched in LDS
+
+template <typename real> struct EvalArgs {
+  uint64_t R, p0;              // query rows of this launch; their first row in the P tables
+  uint64_t n, npop, per;       // items, popularity entries, items per slice (multiple of REC_IT)
+  int C, seen;
+  uint32_t S, rt;              // item slices; row tiles of this launch (work items: slice-major)
+  const real *const *P;
+  const real *const *Q;
+  const real *a, *b;           // a_i of the query rows, b_j
+  const uint8_t *cold;         // per query row
+  const double *popular;
+  const int64_t *sptr;         // sorted, distinct seen items < n of each query row
+  const uint32_t *scol;
+  const int64_t *kptr;         // each query row's labels in kv / kj / cnt
+  const double *kv;            // label scores and items, each row's sorted by the ranking order
+  const uint32_t *kj;
+  uint32_t *cnt;               // per label: candidates between the label before it and itself
+};
+
+template <typename real, int KP>
+__global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
+  using M = RecMma<real>;
+  using V = typename M::V;
+  constexpr int GR = M::GR;
+  __shared__ double sc[REC_RT][REC_IT + 1];
+  __shared__ uint32_t cnt[REC_RT][EV_CAP];
+  __shared__ double last_v[REC_RT];  // each row's last label
+  __shared__ uint32_t last_j[REC_RT];
+  __shared__ int64_t k0[REC_RT];
+  __shared__ int kn[REC_RT];
+  __shared__ double lkv[REC_RT][EV_LC];  // the labels of a row with at most EV_LC of them
+  __shared__ uint32_t lkj[REC_RT][EV_LC];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int m = lane & 15, q = lane >> 4;
+  const unsigned L = blockIdx.x;
+  if (L >= g.rt * g.S) return;
+  const uint64_t r0 = (uint64_t)(L % g.rt) * REC_RT;
+  const uint64_t sl = L / g.rt;
+  const uint64_t jb = sl * g.per < g.n ? sl * g.per : g.n;
+  const uint64_t je = jb + g.per < g.n ? jb + g.per : g.n;
+  const int depth = g.C * KP, nch = (depth + 15) / 16;
+  for (int t = threadIdx.x; t < REC_RT * EV_CAP; t += BLOCK) cnt[t / EV_CAP][t % EV_CAP] = 0;
+  for (int t = threadIdx.x; t < REC_RT * EV_LC; t += BLOCK) {
+    const uint64_t i = r0 + t / EV_LC;
+    const int p = t % EV_LC;
+    const int64_t b0 = i < g.R ? g.kptr[i] : 0, b1 = i < g.R ? g.kptr[i + 1] : 0;
+    const bool in = b1 - b0 <= EV_LC && p < b1 - b0;
+    lkv[t / EV_LC][p] = in ? g.kv[b0 + p] : 0.0;
+    lkj[t / EV_LC][p] = in ? g.kj[b0 + p] : 0u;
+  }
+  if (threadIdx.x < REC_RT) {
+    const uint64_t i = r0 + threadIdx.x;
+    const int64_t b0 = i < g.R ? g.kptr[i] : 0, b1 = i < g.R ? g.kptr[i + 1] : 0;
+    k0[threadIdx.x] = b0;
+    kn[threadIdx.x] = (int)(b1 - b0);
+    last_v[threadIdx.x] = b1 > b0 ? g.kv[b1 - 1] : 0.0;
+    last_j[threadIdx.x] = b1 > b0 ? g.kj[b1 - 1] : 0u;
+  }
+  __syncthreads();
+  {  // a row tile without labels has nothing to count (block-uniform)
+    int any = 0;
+    for (int t = 0; t < REC_RT; t++) any |= kn[t];
+    if (!any) return;
+  }
+  const uint64_t ra0 = r0 + m, ra1 = r0 + 16 + m;
+  const bool ha0 = ra0 < g.R, ha1 = ra1 < g.R;
+  real ai[2][4];
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const uint64_t i = r0 + 16 * h + M::drow(q, r);
+      ai[h][r] = i < g.R ? g.a[i] : (real)0;
+    }
+  unsigned coldbits = 0;
+  for (int rr = 0; rr < REC_RT / 4; rr++) {
+    const uint64_t i = r0 + w * (REC_RT / 4) + rr;
+    if (i < g.R && g.cold[i]) coldbits |= 1u << rr;
+  }
+  const V zero = {(real)0, (real)0, (real)0, (real)0};
+  uint64_t jq = jb + (uint64_t)w * 16 + m;
+  bool hb = jq < je;
+  V bq[2][GR], a0q[2][GR], a1q[2][GR];
+  auto load = [&](auto SB_, int c0) {
+    constexpr int sb = decltype(SB_)::value;
+#pragma unroll
+    for (int u = 0; u < GR; u++) {
+      const int d = 16 * (c0 + u) + 4 * q;
+      const bool in = d < depth;
+      const int tb = in ? d / KP : 0, e = d % KP;
+      bq[sb][u] = (in && hb) ? M::ld(g.Q[tb] + jq * KP + e) : zero;
+      a0q[sb][u] = (in && ha0) ? M::ld(g.P[tb] + (g.p0 + ra0) * KP + e) : zero;
+      a1q[sb][u] = (in && ha1) ? M::ld(g.P[tb] + (g.p0 + ra1) * KP + e) : zero;
+    }
+  };
+  // k_rec_topn's chain: the same bits for the same (row, item)
+  auto mma = [&](auto SB_, int c0, V &acc0, V &acc1) {
+    constexpr int sb = decltype(SB_)::value;
+#pragma unroll
+    for (int u = 0; u < GR; u++)
+      if (c0 + u < nch) {
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+          acc0 = M::mma(a0q[sb][u][s], bq[sb][u][s], acc0);
+          acc1 = M::mma(a1q[sb][u][s], bq[sb][u][s], acc1);
+        }
+      }
+  };
+  load(std::integral_constant<int, 0>(), 0);
+  for (uint64_t t0 = jb; t0 < je; t0 += REC_IT) {
+    V acc0 = zero, acc1 = zero;
+    const real bj = hb ? g.b[jq] : (real)0;
+    for (int c0 = 0; c0 < nch; c0 += 2 * GR) {
+      load(std::integral_constant<int, 1>(), c0 + GR);
+      mma(std::integral_constant<int, 0>(), c0, acc0, acc1);
+      if (c0 + GR >= nch) break;
+      load(std::integral_constant<int, 0>(), c0 + 2 * GR);
+      mma(std::integral_constant<int, 1>(), c0 + GR, acc0, acc1);
+    }
+    jq += REC_IT;
+    hb = jq < je;
+    if (t0 + REC_IT < je) load(std::integral_constant<int, 0>(), 0);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int i0 = M::drow(q, r);
+      sc[i0][w * 16 + m] = (double)((acc0[r] + bj) + ai[0][r]);
+      sc[16 + i0][w * 16 + m] = (double)((acc1[r] + bj) + ai[1][r]);
+    }
+    __syncthreads();
+    // counting: wave w, rows 8 w .. 8 w + 7, lane = the tile's item
+    const uint64_t j = t0 + lane;
+    for (int rr = 0; rr < REC_RT / 4; rr++) {
+      const int il = w * (REC_RT / 4) + rr;
+      const uint64_t i = r0 + il;
+      if (i >= g.R) break;  // (wave-uniform)
+      const int np = kn[il];
+      if (np == 0) continue;
+      double v = REC_NEG_INF;
+      bool cand = j < je;
+      if (coldbits >> rr & 1) {
+        cand = cand && j < g.npop;
+        if (cand) v = g.popular[j];
+      } else {
+        v = sc[il][lane];
+      }
+      cand = cand && rec_better(v, (uint32_t)j, last_v[il], last_j[il]);
+      if (cand && g.seen) {  // binary search in the row's sorted seen items
+        int64_t lo = g.sptr[i], hiq = g.sptr[i + 1];
+        const int64_t end = hiq;
+        while (lo < hiq) {
+          const int64_t mid = (lo + hiq) >> 1;
+          if (g.scol[mid] < (uint32_t)j) lo = mid + 1;
+          else hiq = mid;
+        }
+        if (lo < end && g.scol[lo] == (uint32_t)j) cand = false;
+      }
+      const uint64_t mask = __ballot(cand);
+      if (!mask) continue;
+      const int64_t kb = k0[il];
+      int t = 0;
+      if (cand) {  // the first label it ranks before (it ranks before the last one)
+        int lo = 0, hi = np - 1;
+        if (np <= EV_LC) {
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (rec_better(v, (uint32_t)j, lkv[il][mid], lkj[il][mid])) hi = mid;
+            else lo = mid + 1;
+          }
+        } else {
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (rec_better(v, (uint32_t)j, g.kv[kb + mid], g.kj[kb + mid])) hi = mid;
+            else lo = mid + 1;
+          }
+        }
+        t = lo;
+      }
+      const int first = __ffsll((unsigned long long)mask) - 1;
+      const int tf = (int)rec_lane((uint32_t)t, first);
+      const bool one = __ballot(cand && t != tf) == 0;  // the whole tile before the same label
+      const uint32_t add = one ? (uint32_t)__popcll(mask) : 1u;
+      if (one ? lane == first : cand) {
+        if (np <= EV_CAP) atomicAdd(&cnt[il][t], add);
+        else atomicAdd(g.cnt + kb + t, add);
+      }
+    }
+    __syncthreads();
+  }
+  // (a row's LDS counters are written by the row's wave only)
+  for (int rr = 0; rr < REC_RT / 4; rr++) {
+    const int il = w * (REC_RT / 4) + rr;
+    const int np = kn[il];
+    if (np == 0 || np > EV_CAP) continue;
+    for (int p = lane; p < np; p += 64) {
+      const uint32_t c = cnt[il][p];
+      if (c) atomicAdd(g.cnt + k0[il] + p, c);
+    }
+  }
+}
+
 }  // namespace ocffm

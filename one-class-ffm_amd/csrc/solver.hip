@@ -343,6 +343,8 @@ struct ProblemBase {
   virtual uint64_t test_rows() const = 0;
   virtual void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags,
                          uint32_t *items, double *scores) = 0;
+  virtual void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
+                           uint32_t *ncand) = 0;
   virtual uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) = 0;
   virtual void set(char what, uint32_t b12, const double *in, uint64_t len) = 0;
   virtual void grad(uint32_t f1, uint32_t f2, int half, double *out) = 0;
@@ -1016,6 +1018,250 @@ template <typename real> class Problem final : public ProblemBase {
     }
   }
 
+  // ------------------------------------- query rows (recommend, evaluate)
+  // Rows [row0, row0 + rows) of a file X in the train field space, laid out
+  // for the fused scoring kernels: the per-field CSR (build_fields with the
+  // train Ds), the projections P_c through utx, a_i, the cold flags, and the
+  // sorted distinct items < n of each row of `lab` (the labels to leave out;
+  // NULL: none).
+  struct RecRows {
+    DevSide<real> Xs;
+    std::vector<DevBuf<real>> Px;
+    DevBuf<real *> pt;
+    DevBuf<real> ax;  // a_i (zero without the side blocks)
+    std::vector<uint8_t> cold;
+    DevBuf<uint8_t> dcold;
+    std::vector<int64_t> lptr;
+    std::vector<uint32_t> lcol;
+    DevBuf<int64_t> dlptr;
+    DevBuf<uint32_t> dlcol;
+  };
+  void rec_check(const HostData &X, uint64_t row0, uint64_t rows) {
+    if (X.f > fu_) throw Error(OCFFM_E_ARG, "X has more fields than the train set's user side");
+    for (uint64_t p = X.raw.xptr[row0]; p < X.raw.xptr[row0 + rows]; p++)
+      if (X.raw.fid[p] >= fu_ || X.raw.idx[p] >= U_.Ds[X.raw.fid[p]])
+        throw Error(OCFFM_E_DATA, "X has a node with idx >= Ds[fid] (read it with the train Ds)");
+  }
+  void rec_layout(RecRows &L, const HostData &X, uint64_t row0, uint64_t rows, const HostData *lab) {
+    DevSide<real> &Xs = L.Xs;
+    Xs.R = Xs.R_glob = rows;
+    Xs.row0 = row0;
+    {
+      dev::Builder B(stream_);
+      build_fields(Xs, X, row0, row0 + rows, U_.Ds, B);
+      B.sync();
+    }
+    L.Px.resize(std::max<uint32_t>(C_, 1));
+    std::vector<real *> tl(std::max<uint32_t>(C_, 1), nullptr);
+    for (uint32_t c = 0, f1 = 0; f1 < fu_; f1++)
+      for (uint32_t f2 = fu_; f2 < f_; f2++, c++) {
+        L.Px[c].alloc(rows * kp_, false);
+        utx(Xs, f1, W_[block_index(f1, f2, f_)].p, L.Px[c].p);
+        tl[c] = L.Px[c].p;
+      }
+    L.pt.upload(tl);
+    L.ax.alloc(rows);
+    if (prm_.self_side) {
+      DevBuf<real> p1, p2;
+      p1.alloc(rows * kp_, false);
+      p2.alloc(rows * kp_, false);
+      for (uint32_t f1 = 0; f1 < fu_; f1++)
+        for (uint32_t f2 = f1; f2 < fu_; f2++) {
+          const uint32_t b12 = block_index(f1, f2, f_);
+          utx(Xs, f1, W_[b12].p, p1.p);
+          utx(Xs, f2, H_[b12].p, p2.p);
+          rowdot_add(rows, p1.p, p2.p, L.ax.p);
+        }
+      sync();  // (p1 / p2 are freed here)
+    }
+    L.cold.resize(rows);
+    for (uint64_t i = 0; i < rows; i++) L.cold[i] = X.nnx[row0 + i] == 0;
+    L.dcold.upload(L.cold);
+    L.lptr.assign(rows + 1, 0);
+    L.lcol.clear();
+    if (lab)
+      for (uint64_t i = 0; i < rows; i++) {
+        const size_t b = L.lcol.size();
+        for (uint64_t p = lab->yptr[row0 + i]; p < lab->yptr[row0 + i + 1]; p++)
+          if (lab->ycol[p] < n_) L.lcol.push_back((uint32_t)lab->ycol[p]);
+        std::sort(L.lcol.begin() + b, L.lcol.end());
+        L.lcol.erase(std::unique(L.lcol.begin() + b, L.lcol.end()), L.lcol.end());
+        L.lptr[i + 1] = (int64_t)L.lcol.size();
+      }
+    if (L.lcol.empty()) L.lcol.push_back(0);
+    L.dlptr.upload(L.lptr);
+    L.dlcol.upload(L.lcol);
+  }
+
+  // ------------------------------------------------- ranking evaluation
+  // Exact rank of every label of X among its row's candidates (ocffm.h
+  // ocffm_problem_label_ranks).  The distinct candidate labels of every row
+  // are scored on their own (k_eval_label_scores), sorted per row on the host
+  // by the ranking order, and one sweep over the items (k_eval_count, rows in
+  // chunks, items in slices as in recommend) counts the candidates that fall
+  // between consecutive labels; the prefix sums are the ranks.
+  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
+                   uint32_t *ncand) override {
+    need_init();
+    if (!ranks) throw Error(OCFFM_E_ARG, "null ranks");
+    if (!X.has_label || X.yptr.size() != X.m + 1) throw Error(OCFFM_E_ARG, "X has no labels");
+    if (seen && (seen->m != X.m || (seen->m && seen->yptr.size() != seen->m + 1)))
+      throw Error(OCFFM_E_ARG, "seen must have X's row count (and labels)");
+    if (X.m >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many rows");
+    const uint64_t rows = X.m;
+    rec_check(X, 0, rows);
+    if (rows == 0) return;
+    sync_owned();
+    sync();
+    const auto th0 = std::chrono::steady_clock::now();
+    RecRows L;
+    rec_layout(L, X, 0, rows, seen);
+    const uint64_t npop = std::min<uint64_t>(npop_, n_);
+    // each row's distinct candidate labels; every label's place among them
+    const uint64_t ny = X.yptr[rows];
+    std::vector<int64_t> kptr(rows + 1, 0);
+    std::vector<uint32_t> krow, kitem;
+    std::vector<int64_t> where(ny, -1);  // label entry -> its kept label (-1: not a candidate)
+    {
+      std::vector<std::pair<uint32_t, uint64_t>> tmp;
+      for (uint64_t i = 0; i < rows; i++) {
+        const uint64_t lim = L.cold[i] ? npop : n_;
+        const uint32_t *sb = L.lcol.data() + L.lptr[i], *se = L.lcol.data() + L.lptr[i + 1];
+        if (ncand) ncand[i] = (uint32_t)(lim - (uint64_t)(std::lower_bound(sb, se, (uint32_t)lim) - sb));
+        tmp.clear();
+        for (uint64_t p = X.yptr[i]; p < X.yptr[i + 1]; p++) {
+          const uint64_t j = X.ycol[p];
+          if (j < lim && !std::binary_search(sb, se, (uint32_t)j)) tmp.push_back({(uint32_t)j, p});
+        }
+        std::sort(tmp.begin(), tmp.end());
+        for (size_t t = 0; t < tmp.size(); t++) {
+          if (t == 0 || tmp[t].first != tmp[t - 1].first) {
+            krow.push_back((uint32_t)i);
+            kitem.push_back(tmp[t].first);
+          }
+          where[tmp[t].second] = (int64_t)kitem.size() - 1;
+        }
+        kptr[i + 1] = (int64_t)kitem.size();
+      }
+    }
+    const uint64_t nk = kitem.size();
+    for (uint64_t p = 0; p < ny; p++) {
+      ranks[p] = OCFFM_RANK_NONE;
+      if (scores) scores[p] = -std::numeric_limits<double>::infinity();
+    }
+    if (nk == 0) {
+      counters["eval_setup_us"] =
+          (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
+      return;
+    }
+    DevBuf<uint32_t> dkrow, dkitem, dcnt;
+    DevBuf<int64_t> dkptr;
+    DevBuf<double> dkv;
+    dkrow.upload(krow);
+    dkitem.upload(kitem);
+    dkptr.upload(kptr);
+    dkv.alloc(nk, false);
+    dcnt.alloc(nk);
+    // chunking and slicing (recommend's, with this kernel's residency)
+    const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
+    const uint64_t rt = (chunk + REC_RT - 1) / REC_RT;
+    uint64_t S = rec_slices_;
+    if (!S) {
+      unsigned slots = 2 * ncu_;
+      with_kp(kp_, [&](auto K) { slots = resident(k_eval_count<real, decltype(K)::value>, 0); });
+      S = std::max<uint64_t>(1, slots / rt);
+      S = std::min<uint64_t>(S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
+      S = std::clamp<uint64_t>(S, 1, 64);
+    }
+    const uint64_t per = ((n_ + S - 1) / S + REC_IT - 1) / REC_IT * REC_IT;
+    sync();
+    counters["eval_setup_us"] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
+    const double depth = (double)C_ * kp_;
+    // the labels' own scores
+    prof_launch("evaluate", (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
+      with_kp(kp_, [&](auto K) {
+        constexpr int KP = decltype(K)::value;
+        launch(k_eval_label_scores<real, KP>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)C_,
+               (const real *const *)L.pt.p, (const real *const *)(tabs_.p + C_), (const real *)L.ax.p,
+               (const real *)V_.bias.p, (const uint8_t *)L.dcold.p, (const double *)popular_.p,
+               (const uint32_t *)dkrow.p, (const uint32_t *)dkitem.p, dkv.p);
+      });
+    }, 2.0 * (double)nk * depth);
+    std::vector<double> kv(nk);
+    HIPCHK(hipMemcpyAsync(kv.data(), dkv.p, nk * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    sync();
+    // each row's labels in ranking order
+    std::vector<uint32_t> ord(nk);
+    for (uint64_t e = 0; e < nk; e++) ord[e] = (uint32_t)e;
+    for (uint64_t i = 0; i < rows; i++)
+      std::sort(ord.begin() + kptr[i], ord.begin() + kptr[i + 1], [&](uint32_t x, uint32_t y) {
+        return kv[x] > kv[y] || (kv[x] == kv[y] && kitem[x] < kitem[y]);
+      });
+    std::vector<double> sv(nk);
+    std::vector<uint32_t> sj(nk);
+    for (uint64_t e = 0; e < nk; e++) {
+      sv[e] = kv[ord[e]];
+      sj[e] = kitem[ord[e]];
+    }
+    DevBuf<double> dsv;
+    DevBuf<uint32_t> dsj;
+    dsv.upload(sv);
+    dsj.upload(sj);
+    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
+      const uint64_t cr = std::min(chunk, rows - c0);
+      if (kptr[c0 + cr] == kptr[c0]) continue;  // no label in these rows
+      EvalArgs<real> g{};
+      g.R = cr;
+      g.p0 = c0;
+      g.n = n_;
+      g.npop = npop;
+      g.per = per;
+      g.C = (int)C_;
+      g.seen = seen ? 1 : 0;
+      g.S = (uint32_t)S;
+      g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
+      g.P = L.pt.p;
+      g.Q = tabs_.p + C_;
+      g.a = L.ax.p + c0;
+      g.b = V_.bias.p;
+      g.cold = L.dcold.p + c0;
+      g.popular = popular_.p;
+      g.sptr = L.dlptr.p + c0;
+      g.scol = L.dlcol.p;
+      g.kptr = dkptr.p + c0;
+      g.kv = dsv.p;
+      g.kj = dsj.p;
+      g.cnt = dcnt.p;
+      const double bytes = ((double)cr + (double)n_) * depth * sizeof(real) + (double)n_ * sizeof(real) +
+                           (double)(kptr[c0 + cr] - kptr[c0]) * (sizeof(double) + 2 * sizeof(uint32_t));
+      prof_launch("evaluate", bytes, [&] {
+        with_kp(kp_, [&](auto K) {
+          constexpr int KP = decltype(K)::value;
+          launch(k_eval_count<real, KP>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
+        });
+      }, 2.0 * (double)cr * (double)n_ * depth);
+    }
+    std::vector<uint32_t> cnt(nk);
+    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+    sync();
+    flush_prof();
+    // ranks: the prefix sums of each row's counters, back in label order
+    std::vector<uint32_t> krank(nk);
+    for (uint64_t i = 0; i < rows; i++) {
+      uint32_t run = 0;
+      for (int64_t e = kptr[i]; e < kptr[i + 1]; e++) {
+        run += cnt[e];
+        krank[ord[e]] = run;
+      }
+    }
+    for (uint64_t p = 0; p < ny; p++)
+      if (where[p] >= 0) {
+        ranks[p] = krank[where[p]];
+        if (scores) scores[p] = kv[where[p]];
+      }
+  }
+
   // ---------------------------------------------------- recommendation
   // Top-N items of rows [row0, row0 + rows) of X (ocffm.h
   // ocffm_problem_recommend).  The rows' user-side layout is built as a test
@@ -1028,71 +1274,19 @@ template <typename real> class Problem final : public ProblemBase {
     if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
     if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
     if (!items) throw Error(OCFFM_E_ARG, "null items");
-    if (X.f > fu_) throw Error(OCFFM_E_ARG, "X has more fields than the train set's user side");
+    rec_check(X, row0, rows);
     if (rows == 0) return;
-    const uint64_t r1 = row0 + rows;
-    for (uint64_t p = X.raw.xptr[row0]; p < X.raw.xptr[r1]; p++)
-      if (X.raw.fid[p] >= fu_ || X.raw.idx[p] >= U_.Ds[X.raw.fid[p]])
-        throw Error(OCFFM_E_DATA, "X has a node with idx >= Ds[fid] (read it with the train Ds)");
     sync_owned();
     sync();
     const auto th0 = std::chrono::steady_clock::now();
-    // the rows' layout and projections
-    DevSide<real> Xs;
-    Xs.R = Xs.R_glob = rows;
-    Xs.row0 = row0;
-    {
-      dev::Builder B(stream_);
-      build_fields(Xs, X, row0, r1, U_.Ds, B);
-      B.sync();
-    }
-    std::vector<DevBuf<real>> Px(std::max<uint32_t>(C_, 1));
-    std::vector<real *> tl(std::max<uint32_t>(C_, 1), nullptr);
-    for (uint32_t c = 0, f1 = 0; f1 < fu_; f1++)
-      for (uint32_t f2 = fu_; f2 < f_; f2++, c++) {
-        Px[c].alloc(rows * kp_, false);
-        utx(Xs, f1, W_[block_index(f1, f2, f_)].p, Px[c].p);
-        tl[c] = Px[c].p;
-      }
-    DevBuf<real *> pt;
-    pt.upload(tl);
-    DevBuf<real> ax;  // a_i (zero without the side blocks)
-    ax.alloc(rows);
-    if (prm_.self_side) {
-      DevBuf<real> p1, p2;
-      p1.alloc(rows * kp_, false);
-      p2.alloc(rows * kp_, false);
-      for (uint32_t f1 = 0; f1 < fu_; f1++)
-        for (uint32_t f2 = f1; f2 < fu_; f2++) {
-          const uint32_t b12 = block_index(f1, f2, f_);
-          utx(Xs, f1, W_[b12].p, p1.p);
-          utx(Xs, f2, H_[b12].p, p2.p);
-          rowdot_add(rows, p1.p, p2.p, ax.p);
-        }
-      sync();  // (p1 / p2 are freed here)
-    }
-    std::vector<uint8_t> cold(rows);
-    for (uint64_t i = 0; i < rows; i++) cold[i] = X.nnx[row0 + i] == 0;
-    DevBuf<uint8_t> dcold;
-    dcold.upload(cold);
-    // each row's labels < n, sorted and distinct
     const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
-    std::vector<int64_t> lptr(rows + 1, 0);
-    std::vector<uint32_t> lcol;
-    if (excl)
-      for (uint64_t i = 0; i < rows; i++) {
-        const size_t b = lcol.size();
-        for (uint64_t p = X.yptr[row0 + i]; p < X.yptr[row0 + i + 1]; p++)
-          if (X.ycol[p] < n_) lcol.push_back((uint32_t)X.ycol[p]);
-        std::sort(lcol.begin() + b, lcol.end());
-        lcol.erase(std::unique(lcol.begin() + b, lcol.end()), lcol.end());
-        lptr[i + 1] = (int64_t)lcol.size();
-      }
-    if (lcol.empty()) lcol.push_back(0);
-    DevBuf<int64_t> dlptr;
-    DevBuf<uint32_t> dlcol;
-    dlptr.upload(lptr);
-    dlcol.upload(lcol);
+    RecRows L;
+    rec_layout(L, X, row0, rows, excl ? &X : nullptr);
+    DevBuf<real *> &pt = L.pt;
+    DevBuf<real> &ax = L.ax;
+    DevBuf<uint8_t> &dcold = L.dcold;
+    DevBuf<int64_t> &dlptr = L.dlptr;
+    DevBuf<uint32_t> &dlcol = L.dlcol;
     // chunking and slicing
     const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
     const uint64_t rt = (chunk + REC_RT - 1) / REC_RT;
@@ -4363,6 +4557,102 @@ int ocffm_problem_test_rows(ocffm_problem *prob, uint64_t *m) {
 int ocffm_problem_recommend(ocffm_problem *prob, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
                             uint32_t flags, uint32_t *items, double *scores) {
   PROB_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); prob->p->recommend(X->d, row0, rows, topn, flags, items, scores));
+}
+int ocffm_problem_label_ranks(ocffm_problem *prob, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
+                              double *scores, uint32_t *ncand) {
+  PROB_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
+            prob->p->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand));
+}
+
+static void check_cuts(const uint32_t *cuts, uint32_t ncut) {
+  if (!cuts || ncut < 1 || ncut > OCFFM_EVAL_MAX_CUTS) throw Error(OCFFM_E_ARG, "ncut must be in 1..OCFFM_EVAL_MAX_CUTS");
+  for (uint32_t s = 0; s < ncut; s++)
+    if (cuts[s] < 1 || (s && cuts[s] <= cuts[s - 1])) throw Error(OCFFM_E_ARG, "cuts must be >= 1 and strictly increasing");
+}
+
+// ocffm.h ocffm_eval_from_ranks: the definitions are stated there.
+static void eval_from_ranks(uint64_t m, const uint64_t *yptr, const uint32_t *ranks, const double *scores,
+                            const uint32_t *ncand, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
+  if (!out) throw Error(OCFFM_E_ARG, "null output");
+  check_cuts(cuts, ncut);
+  if (!yptr || !ncand || (!ranks && yptr[m] != yptr[0])) throw Error(OCFFM_E_ARG, "null yptr / ranks / ncand");
+  *out = ocffm_eval{};
+  out->rows = m;
+  out->labels = yptr[m] - yptr[0];
+  out->ncut = ncut;
+  for (uint32_t s = 0; s < ncut; s++) out->cuts[s] = cuts[s];
+  double ploss = 0, mrr = 0, auc = 0;
+  double prec[OCFFM_EVAL_MAX_CUTS] = {}, recall[OCFFM_EVAL_MAX_CUTS] = {}, ndcg[OCFFM_EVAL_MAX_CUTS] = {},
+         map[OCFFM_EVAL_MAX_CUTS] = {}, hit[OCFFM_EVAL_MAX_CUTS] = {};
+  uint64_t used = 0, auc_rows = 0;
+  std::vector<std::pair<uint32_t, double>> lab;
+  for (uint64_t i = 0; i < m; i++) {
+    lab.clear();
+    for (uint64_t p = yptr[i]; p < yptr[i + 1]; p++)
+      if (ranks[p] != OCFFM_RANK_NONE) lab.push_back({ranks[p], scores ? scores[p] : 1.0});
+    std::sort(lab.begin(), lab.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    lab.erase(std::unique(lab.begin(), lab.end(), [](const auto &x, const auto &y) { return x.first == y.first; }),
+              lab.end());
+    const uint64_t P = lab.size();
+    if (P == 0) continue;
+    used++;
+    out->labels_ranked += P;
+    for (const auto &l : lab) ploss += (1 - l.second) * (1 - l.second);
+    mrr += 1.0 / ((double)lab[0].first + 1);
+    if ((uint64_t)ncand[i] > P) {
+      double inv = 0;  // non-label candidates before the labels
+      for (uint64_t t = 0; t < P; t++) inv += (double)lab[t].first - (double)t;
+      auc += 1 - inv / ((double)P * (double)(ncand[i] - P));
+      auc_rows++;
+    }
+    for (uint32_t s = 0; s < ncut; s++) {
+      const uint64_t c = cuts[s], top = std::min<uint64_t>(c, P);
+      double hits = 0, dcg = 0, idcg = 0, ap = 0;
+      for (uint64_t t = 0; t < P && lab[t].first < c; t++) {
+        hits += 1;
+        dcg += 1.0 / std::log2((double)lab[t].first + 2);
+        ap += (double)(t + 1) / ((double)lab[t].first + 1);
+      }
+      for (uint64_t t = 0; t < top; t++) idcg += 1.0 / std::log2((double)t + 2);
+      prec[s] += hits / (double)c;
+      recall[s] += hits / (double)P;
+      ndcg[s] += dcg / idcg;
+      map[s] += ap / (double)top;
+      hit[s] += hits > 0 ? 1 : 0;
+    }
+  }
+  out->rows_used = used;
+  if (used == 0) return;
+  out->loss = scores ? std::sqrt(ploss / (double)used) : 0;
+  out->mrr = mrr / (double)used;
+  out->auc = auc_rows ? auc / (double)auc_rows : 0;
+  for (uint32_t s = 0; s < ncut; s++) {
+    out->prec[s] = prec[s] / (double)used;
+    out->recall[s] = recall[s] / (double)used;
+    out->ndcg[s] = ndcg[s] / (double)used;
+    out->map[s] = map[s] / (double)used;
+    out->hit[s] = hit[s] / (double)used;
+  }
+}
+
+int ocffm_eval_from_ranks(uint64_t m, const uint64_t *yptr, const uint32_t *ranks, const double *scores,
+                          const uint32_t *ncand, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
+  return guarded([&] { eval_from_ranks(m, yptr, ranks, scores, ncand, cuts, ncut, out); });
+}
+
+int ocffm_problem_evaluate(ocffm_problem *prob, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
+                           uint32_t ncut, ocffm_eval *out) {
+  return guarded([&] {
+    if (!prob || !prob->p) throw Error(OCFFM_E_ARG, "null problem");
+    if (!X) throw Error(OCFFM_E_ARG, "null X");
+    if (!out) throw Error(OCFFM_E_ARG, "null output");
+    check_cuts(cuts, ncut);
+    const HostData &d = X->d;
+    std::vector<uint32_t> ranks(d.ycol.size() + 1), ncand(d.m + 1);
+    std::vector<double> scores(d.ycol.size() + 1);
+    prob->p->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data());
+    eval_from_ranks(d.m, d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+  });
 }
 int ocffm_problem_save_binary(ocffm_problem *prob, const char *path) { PROB_CALL(prob->p->save_binary(path)); }
 int ocffm_problem_load_binary(ocffm_problem *prob, const char *path) { PROB_CALL(prob->p->load_binary(path)); }

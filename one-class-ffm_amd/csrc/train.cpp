@@ -10,7 +10,10 @@
 //   --device N;
 //   --recommend <file> --topn <n> --rec-out <path> [--rec-unseen]: after the
 //   solve (and any model save) the top-n items of every row of <file> (read
-//   like a -p file) go to <path>, one line of item:score tokens per row.
+//   like a -p file) go to <path>, one line of item:score tokens per row;
+//   --eval <file> [--eval-cuts c1,c2,...] [--eval-seen <file>]: after that,
+//   the ranking metrics of the model on the labelled rows of <file> (read
+//   like a -p file) as one `eval` table on stdout.
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -42,7 +45,10 @@ static std::string usage() {
          "--recommend <path>: after training, recommend items for every row of this file (read like -p)\n"
          "--topn <n>: items per row, 1..128 (default 10)\n"
          "--rec-out <path>: where the recommendations go (one line of item:score per row)\n"
-         "--rec-unseen: leave out each row's own labels\n";
+         "--rec-unseen: leave out each row's own labels\n"
+         "--eval <path>: after training, print ranking metrics on the labelled rows of this file (read like -p)\n"
+         "--eval-cuts <c1,c2,...>: up to 8 increasing cut-offs (default 5,10,20,40,80)\n"
+         "--eval-seen <path>: rows whose labels are left out of the candidates (same row count as --eval)\n";
 }
 
 // train.cpp:22-32: at least one digit somewhere in the token.
@@ -64,7 +70,8 @@ static void check(int st) {
 int main(int argc, char **argv) {
   ocffm_param prm;
   ocffm_param_default(&prm);
-  std::string te_path, model_path, rec_path, rec_out;
+  std::string te_path, model_path, rec_path, rec_out, eval_path, eval_seen;
+  std::vector<uint32_t> eval_cuts{5, 10, 20, 40, 80};
   long topn = 10;
   bool rec_unseen = false;
   try {
@@ -95,10 +102,26 @@ int main(int argc, char **argv) {
       else if (a == "--rec-out") rec_out = value(false, "need to specify path after --rec-out");
       else if (a == "--topn") topn = std::atol(value(true, "need to specify the number of items after --topn"));
       else if (a == "--rec-unseen") rec_unseen = true;
+      else if (a == "--eval") eval_path = value(false, "need to specify path after --eval");
+      else if (a == "--eval-seen") eval_seen = value(false, "need to specify path after --eval-seen");
+      else if (a == "--eval-cuts") {
+        eval_cuts.clear();
+        for (const char *s = value(true, "need to specify cut-offs after --eval-cuts"); *s;) {
+          char *end = nullptr;
+          const long c = std::strtol(s, &end, 10);
+          if (end == s || c < 1 || (*end && *end != ',')) throw std::invalid_argument("--eval-cuts takes c1,c2,... with every c >= 1");
+          eval_cuts.push_back((uint32_t)c);
+          s = *end ? end + 1 : end;
+        }
+      }
       else break;
     }
     if (!rec_path.empty() && rec_out.empty()) throw std::invalid_argument("--recommend needs --rec-out <path>");
     if (topn < 1 || topn > OCFFM_REC_MAX_TOPN) throw std::invalid_argument("--topn must be in 1..128");
+    if (!eval_seen.empty() && eval_path.empty()) throw std::invalid_argument("--eval-seen needs --eval <path>");
+    if (eval_cuts.empty() || eval_cuts.size() > OCFFM_EVAL_MAX_CUTS) throw std::invalid_argument("--eval-cuts takes 1..8 cut-offs");
+    for (size_t s = 1; s < eval_cuts.size(); s++)
+      if (eval_cuts[s] <= eval_cuts[s - 1]) throw std::invalid_argument("--eval-cuts must be strictly increasing");
     if (i >= argc) throw std::invalid_argument("training data not specified");
     if (i + 1 >= argc) throw std::invalid_argument("training data not specified");
     const std::string item_path = argv[i], tr_path = argv[i + 1];
@@ -161,6 +184,28 @@ int main(int argc, char **argv) {
       if (std::fclose(fp) != 0) throw Fail(OCFFM_E_IO, "write failed: " + rec_out);
       ocffm_data_free(X);
       phase("recommend");
+    }
+    if (!eval_path.empty()) {
+      ocffm_data_info info;
+      check(ocffm_data_get_info(U, &info));
+      std::vector<std::uint64_t> ds(info.f ? info.f : 1);
+      check(ocffm_data_get_ds(U, ds.data()));
+      ocffm_data *X = nullptr, *Sn = nullptr;
+      check(ocffm_data_read(eval_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
+      if (!eval_seen.empty()) check(ocffm_data_read(eval_seen.c_str(), 1, ds.data(), (uint32_t)info.f, &Sn));
+      ocffm_eval ev;
+      check(ocffm_problem_evaluate(prob, X, Sn, eval_cuts.data(), (uint32_t)eval_cuts.size(), &ev));
+      std::printf("eval rows %llu rows_used %llu labels %llu labels_ranked %llu\n", (unsigned long long)ev.rows,
+                  (unsigned long long)ev.rows_used, (unsigned long long)ev.labels, (unsigned long long)ev.labels_ranked);
+      std::printf("eval loss %.17g mrr %.17g auc %.17g\n", ev.loss, ev.mrr, ev.auc);
+      std::printf("eval cut prec recall ndcg map hit\n");
+      for (uint32_t s = 0; s < ev.ncut; s++)
+        std::printf("eval %u %.17g %.17g %.17g %.17g %.17g\n", ev.cuts[s], ev.prec[s], ev.recall[s], ev.ndcg[s],
+                    ev.map[s], ev.hit[s]);
+      std::fflush(stdout);
+      ocffm_data_free(X);
+      if (Sn) ocffm_data_free(Sn);
+      phase("evaluate");
     }
     ocffm_problem_destroy(prob);
     ocffm_data_free(U);

@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("OCFFM_LIB") or os.path.join(HERE, "libocffm.so")  # o
 OK, E_ARG, E_IO, E_DATA, E_HIP, E_COMM, E_STATE = range(7)
 FP64, FP32 = 64, 32
 REC_MAX_TOPN, REC_EXCLUDE_LABELS, REC_NONE = 128, 1, 0xFFFFFFFF
+RANK_NONE, EVAL_MAX_CUTS = 0xFFFFFFFF, 8
 COMM_ID_BYTES = 128
 
 
@@ -50,6 +51,23 @@ class _Metrics(C.Structure):
                 ("top_k", C.c_uint32 * 5)]
 
 
+class _Eval(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("rows_used", C.c_uint64), ("labels", C.c_uint64),
+                ("labels_ranked", C.c_uint64), ("ncut", C.c_uint32), ("cuts", C.c_uint32 * 8),
+                ("loss", C.c_double), ("mrr", C.c_double), ("auc", C.c_double), ("prec", C.c_double * 8),
+                ("recall", C.c_double * 8), ("ndcg", C.c_double * 8), ("map", C.c_double * 8),
+                ("hit", C.c_double * 8)]
+
+    def as_dict(self) -> dict:
+        nc = int(self.ncut)
+        d = dict(rows=int(self.rows), rows_used=int(self.rows_used), labels=int(self.labels),
+                 labels_ranked=int(self.labels_ranked), cuts=list(self.cuts[:nc]), loss=self.loss, mrr=self.mrr,
+                 auc=self.auc)
+        for key in ("prec", "recall", "ndcg", "map", "hit"):
+            d[key] = np.array(getattr(self, key)[:nc])
+        return d
+
+
 class _KStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("alg_bytes", C.c_double), ("alg_flops", C.c_double)]
@@ -66,7 +84,7 @@ EXPORTS = [
     "ocffm_problem_validate", "ocffm_print_header", "ocffm_print_epoch", "ocffm_problem_get",
     "ocffm_problem_set", "ocffm_problem_grad", "ocffm_problem_hv", "ocffm_problem_save_model",
     "ocffm_problem_validate_forced", "ocffm_problem_test_rows", "ocffm_problem_save_binary", "ocffm_problem_load_binary",
-    "ocffm_problem_recommend",
+    "ocffm_problem_recommend", "ocffm_problem_label_ranks", "ocffm_eval_from_ranks", "ocffm_problem_evaluate",
     "ocffm_problem_cg_log", "ocffm_problem_set_profiling", "ocffm_problem_set_profile_filter",
     "ocffm_problem_kernel_stats",
     "ocffm_problem_reset_stats", "ocffm_problem_alg_bytes", "ocffm_problem_counter", "ocffm_problem_sync",
@@ -118,6 +136,9 @@ def lib():
     L.ocffm_problem_validate_forced.argtypes = [vp, C.POINTER(_Metrics), vp, u64]
     L.ocffm_problem_test_rows.argtypes = [vp, C.POINTER(u64)]
     L.ocffm_problem_recommend.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp]
+    L.ocffm_problem_label_ranks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ocffm_eval_from_ranks.argtypes = [u64, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_problem_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_problem_save_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_load_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_cg_log.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
@@ -451,6 +472,32 @@ class ImpProblem:
                                              items.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
         return items, scores
 
+    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None):
+        """Exact rank of every label of ``X`` among its row's candidates
+        (include/ocffm.h ocffm_problem_label_ranks): ``(ranks uint32 [nnz_y],
+        scores float64 [nnz_y], ncand uint32 [m])`` in ``X.labels()`` order.
+        ``seen`` (same row count) removes its rows' labels from the candidates;
+        a label that is no candidate has ``RANK_NONE`` / ``-inf``."""
+        i = X.info
+        ranks = np.full(max(1, i["nnz_y"]), RANK_NONE, dtype=np.uint32)
+        scores = np.full(max(1, i["nnz_y"]), -np.inf, dtype=np.float64)
+        ncand = np.zeros(max(1, i["m"]), dtype=np.uint32)
+        _check(lib().ocffm_problem_label_ranks(self.h, X.h, None if seen is None else seen.h, _ptr(ranks),
+                                               _ptr(scores), _ptr(ncand)))
+        return ranks[: i["nnz_y"]], scores[: i["nnz_y"]], ncand[: i["m"]]
+
+    def evaluate(self, X: ImpData, cuts=(5, 10, 20, 40, 80), seen: Optional[ImpData] = None) -> dict:
+        """Ranking metrics of the current model on the labelled rows ``X``
+        (include/ocffm.h ocffm_problem_evaluate): a dict with ``rows``,
+        ``rows_used``, ``labels``, ``labels_ranked``, ``cuts``, ``loss``,
+        ``mrr``, ``auc`` and one array per cut for ``prec``, ``recall``,
+        ``ndcg``, ``map`` and ``hit``."""
+        c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+        e = _Eval()
+        _check(lib().ocffm_problem_evaluate(self.h, X.h, None if seen is None else seen.h, _ptr(c), c.size,
+                                            C.byref(e)))
+        return e.as_dict()
+
     def save_binary(self, path: str) -> None:
         _check(lib().ocffm_problem_save_binary(self.h, path.encode()))
 
@@ -531,6 +578,25 @@ class ImpProblem:
         _check(lib().ocffm_problem_layout_digest(self.h, names, dig, n.value, C.byref(n)))
         raw = names.raw
         return {raw[48 * i:48 * (i + 1)].split(b"\0", 1)[0].decode(): int(dig[i]) for i in range(n.value)}
+
+
+def eval_from_ranks(yptr, ranks, ncand, scores=None, cuts=(5, 10, 20, 40, 80)) -> dict:
+    """Ranking metrics from label ranks (include/ocffm.h ocffm_eval_from_ranks;
+    host code, no GPU): ``yptr`` the m + 1 label offsets, ``ranks`` / ``scores``
+    one entry per label, ``ncand`` one per row."""
+    yp = np.ascontiguousarray(yptr, dtype=np.uint64)
+    rk = np.ascontiguousarray(ranks, dtype=np.uint32)
+    nc = np.ascontiguousarray(ncand, dtype=np.uint32)
+    sc = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64)
+    c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+    m = yp.size - 1
+    if m < 0 or nc.size < m or rk.size < int(yp[-1]) or (sc is not None and sc.size < int(yp[-1])):
+        raise OcffmError(E_ARG, "eval_from_ranks: array sizes do not match yptr")
+    pad = np.zeros(1, dtype=np.uint32)  # (a pointer for empty arrays)
+    e = _Eval()
+    _check(lib().ocffm_eval_from_ranks(m, _ptr(yp), _ptr(rk if rk.size else pad), _ptr(sc),
+                                       _ptr(nc if nc.size else pad), _ptr(c if c.size else pad), c.size, C.byref(e)))
+    return e.as_dict()
 
 
 def srand(seed: int = 1) -> None:
