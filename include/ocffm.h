@@ -247,6 +247,69 @@ int ocffm_problem_recommend(ocffm_problem *p, const ocffm_data *X, uint64_t row0
 int ocffm_problem_label_ranks(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
                               double *scores, uint32_t *ncand);
 
+/* Scores of given pairs (no reference counterpart).  out[e] is the score of
+ * row prow[e] of X and item pitem[e] under the current model, e < npairs: the
+ * value ocffm_problem_recommend and ocffm_problem_label_ranks return for that
+ * (row, item), bit for bit, in either precision (the same chain: chunks of 16
+ * depth elements in order, then (acc + b_j) + a_i, widened to fp64).
+ * X: user rows in the train set's field space (read with the train Ds); its
+ * labels, if any, play no part.  Does not change the solver state.
+ *  - Cold rows: a row with no kept feature node scores popular[j], the train
+ *    popularity value, as in recommend.
+ *  - Pairs that are no candidates: pitem[e] >= n, or >= npop on a cold row,
+ *    score -inf.  Repeated pairs are scored each.
+ *  - Reproducibility: a pair's score does not depend on its place in the call
+ *    nor on the other pairs.
+ *  - Errors: OCFFM_E_STATE before init / load_binary; OCFFM_E_ARG for
+ *    prow[e] >= X.m, a NULL prow / pitem / out with npairs > 0, or an X with
+ *    more fields than the train set's user side; OCFFM_E_DATA for a node of X
+ *    with idx >= Ds[fid] (every row of X is checked and laid out, also those
+ *    no pair names).  npairs == 0 is OCFFM_OK.
+ *  - Sharded problems: as ocffm_problem_recommend.
+ * The launch belongs to the kernel family "rerank" of the statistics below;
+ * the counter "rec_setup_us" holds the last call's host-side set-up time. */
+int ocffm_problem_score(ocffm_problem *p, const ocffm_data *X, uint64_t npairs, const uint32_t *prow,
+                        const uint32_t *pitem, double *out);
+
+/* Top-N of each row's own candidate list (no reference counterpart): what a
+ * retrieval stage, a stock filter or a sampled-negatives harness asks of a
+ * trained model.  For rows [row0, row0 + rows) of X; the list of row
+ * row0 + i is ccol[cptr[i] .. cptr[i + 1]), in any order: cptr holds
+ * rows + 1 non-decreasing offsets with cptr[0] == 0.
+ * items, scores (may be NULL): rows x topn, row-major, with exactly
+ * ocffm_problem_recommend's shape, order and values: score descending, equal
+ * scores by ascending item index, every score the value recommend returns for
+ * that (row, item) bit for bit.  Does not change the solver state.
+ *  - Candidates of a row: the distinct entries of its list that are
+ *    candidates in recommend's sense: < n (every item row of V), or < npop on
+ *    a cold row (scored by train popularity), minus the row's own labels in X
+ *    when OCFFM_REC_EXCLUDE_LABELS is set in flags.  Other entries are
+ *    ignored; a duplicate counts once.
+ *  - Short rows: a row with fewer than topn candidates has OCFFM_REC_NONE and
+ *    a score of -inf in the remaining slots; an empty list gives a row of
+ *    those.
+ *  - Cost: the item rows of the list entries are gathered; no sweep over the
+ *    n items takes place and scratch is (list segments) x topn entries.
+ *  - Reproducibility: a row's result is the same bit for bit between calls
+ *    and does not depend on its position in the call, on the order of its
+ *    list, on OCFFM_REC_ROWS (rows per chunk) nor on how the list was cut
+ *    into segments (OCFFM_REC_SEG): the selection is on the total order
+ *    (score, item index) over distinct items.
+ *  - Errors: those of ocffm_problem_recommend (OCFFM_E_STATE before init /
+ *    load_binary; OCFFM_E_ARG for topn == 0, topn > OCFFM_REC_MAX_TOPN,
+ *    row0 + rows > X.m, NULL items, or an X with more fields than the train
+ *    set's user side; OCFFM_E_DATA for a node of X with idx >= Ds[fid]), and
+ *    OCFFM_E_ARG for a NULL cptr, cptr[0] != 0, a decreasing cptr, or a NULL
+ *    ccol with cptr[rows] > 0.  rows == 0 is OCFFM_OK.
+ *  - Sharded problems: the owned tables are made whole first, as in
+ *    validate; X is not sharded, each rank scores the rows it passes.  This
+ *    has only been run on one rank.
+ * The launches are the kernel family "rerank" of the statistics below; the
+ * counter "rec_setup_us" holds the last call's host-side set-up time. */
+int ocffm_problem_recommend_among(ocffm_problem *p, const ocffm_data *X, uint64_t row0, uint64_t rows,
+                                  const uint64_t *cptr, const uint32_t *ccol, uint32_t topn, uint32_t flags,
+                                  uint32_t *items, double *scores);
+
 /* Ranking metrics from label ranks.  ocffm_eval_from_ranks is pure host code
  * (no GPU, no problem): yptr holds the m + 1 label offsets of the rows,
  * ranks / scores (may be NULL: loss 0) / ncand the outputs of

@@ -4585,4 +4585,205 @@ __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
   }
 }
 
+// ------------------------------------------- top-N among candidate lists ---
+// Top-N of each query row's own candidate list
+// (ocffm_problem_recommend_among).  The work is a gather of item rows, not a
+// dense product: no two rows share an item tile, so k_rec_topn's tiling does
+// not apply.
+//
+// k_rerank: one wave owns one work item, a segment of one row's list, and
+// walks it 16 candidates at a time.  Lane l holds 4 consecutive depth
+// elements (starting at 16 c + 4 (l >> 4) of chunk c) of the wave's one query
+// row on the A side and of candidate l & 15's item row on the B side
+// (k_eval_label_scores's operand layout with one row for all 16 pairs), and
+// runs k_rec_topn's chain: chunks in order, four MFMAs per chunk, then
+// (acc + b_j) + a_i.  Every row of the 16 x 16 product is the query row, so
+// each lane reads candidate l & 15's score from its first D register; an
+// output element depends only on its own row and item, hence the bits are
+// those of recommend.  The query row's first RR_NA chunks stay in registers
+// for the whole segment (the kkbox depth, 6 x 32, is exactly RR_NA chunks);
+// chunks past them re-read it (it stays in the vector L1).  The item rows of
+// those chunks are all requested before the first MFMA: up to RR_NA 16- or
+// 32-byte loads per lane in flight.
+// Selection: rec_insert's sorted list (two entries per lane) and the row's
+// N-th entry live in registers for the whole segment: no LDS, no barrier.  A
+// candidate is an entry < n (cold rows: < npop, score popular[j]) that is not
+// among the row's sorted labels (exclude).  A copy of an entry already seen
+// is either still in the list (one ballot on item equality) or no better than
+// the N-th entry (equal items have equal scores), so a duplicate counts once.
+// A row with one work item writes its result; the others write partial lists
+// that k_rerank_merge offers, in work item order, to one list per row under
+// the same rules, so copies in different segments count once as well.
+// Selection is on the strict total order (score, item) over distinct items,
+// hence independent of the list's order and of how it was split.
+// Ragged edges: list entries outside a work item's range are never read, nor
+// are item rows of entries that are no candidates.
+constexpr int RR_NA = 12;
+
+template <typename real> struct RerankArgs {
+  uint64_t W, w0;              // work items of this launch; the first one's index in wrow / wbeg / wlen
+  uint64_t r0, c0;             // first row of this launch (out is relative to it); first list entry in ccol
+  uint64_t n, npop;
+  int C, topn, exclude;
+  const real *const *P;        // C user-side cross tables of the call's rows
+  const real *const *Q;        // C item-side cross tables (n x KP)
+  const real *a, *b;           // a_i of the call's rows, b_j
+  const uint8_t *cold;         // per row of the call
+  const double *popular;
+  const int64_t *lptr;         // sorted, distinct labels < n of each row of the call (exclude)
+  const uint32_t *lcol;
+  const int64_t *wptr;         // per row of the call: its work items [wptr[i], wptr[i + 1])
+  const uint32_t *wrow;        // work item -> row of the call
+  const uint64_t *wbeg;        // work item -> its first list entry (an index of the call's ccol)
+  const uint32_t *wlen;        // work item -> entries
+  const uint32_t *ccol;        // this launch's list entries (entry c0 first)
+  double *part_v, *out_v;      // W x topn partial lists; rows x topn results
+  uint32_t *part_j, *out_j;
+};
+
+// Offer the candidates of the lanes in mask (score v, item j) to the sorted
+// list in (v0, j0), (v1, j1), whose topn-th entry is (tv, tj).  Wave-uniform.
+__device__ __forceinline__ void rerank_offer(uint64_t mask, double v, uint32_t j, double &v0, uint32_t &j0,
+                                             double &v1, uint32_t &j1, double &tv, uint32_t &tj, int topn,
+                                             int lane) {
+  const int tl = (topn - 1) & 63;
+  const bool hi = topn > 64;
+  while (mask) {
+    const int src = __ffsll((unsigned long long)mask) - 1;
+    mask &= mask - 1;
+    const double cv = rec_lane(v, src);
+    const uint32_t cj = rec_lane(j, src);
+    if (!rec_better(cv, cj, tv, tj)) continue;   // the threshold has moved past it (or it is a copy below it)
+    if (__ballot(j0 == cj || j1 == cj)) continue;  // a copy that is in the list
+    rec_insert(cv, cj, v0, j0, v1, j1, lane);
+    tv = hi ? rec_lane(v1, tl) : rec_lane(v0, tl);
+    tj = hi ? rec_lane(j1, tl) : rec_lane(j0, tl);
+  }
+}
+
+template <typename real, int KP>
+__global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
+  using M = RecMma<real>;
+  using V = typename M::V;
+  const int lane = threadIdx.x & 63;
+  const int m = lane & 15, q = lane >> 4;
+  const uint64_t wl = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+  if (wl >= g.W) return;  // (wave-uniform)
+  const uint64_t w = g.w0 + wl;
+  const uint64_t i = g.wrow[w];
+  const uint64_t cb = g.wbeg[w] - g.c0;
+  const uint32_t len = g.wlen[w];
+  const bool cold = g.cold[i] != 0;
+  const uint64_t lim = cold ? g.npop : g.n;
+  const int depth = g.C * KP, nch = (depth + 15) / 16;
+  const V zero = {(real)0, (real)0, (real)0, (real)0};
+  V aq[RR_NA];
+#pragma unroll
+  for (int c = 0; c < RR_NA; c++) {
+    const int d = 16 * c + 4 * q;
+    const bool in = d < depth && !cold;
+    const int tb = d < depth ? d / KP : 0, el = d % KP;
+    aq[c] = in ? M::ld(g.P[tb] + i * KP + el) : zero;
+  }
+  const real ai = g.a[i];
+  const int64_t lb = g.exclude ? g.lptr[i] : 0, le = g.exclude ? g.lptr[i + 1] : 0;
+  double v0 = REC_NEG_INF, v1 = REC_NEG_INF, tv = REC_NEG_INF;
+  uint32_t j0 = REC_NONE, j1 = REC_NONE, tj = REC_NONE;
+  uint32_t jn = (uint32_t)m < len ? g.ccol[cb + m] : REC_NONE;
+  for (uint32_t t0 = 0; t0 < len; t0 += 16) {
+    const bool have = t0 + m < len;
+    const uint32_t j = jn;
+    // the next 16 entries are on their way while these are scored
+    jn = (uint64_t)t0 + 16 + m < len ? g.ccol[cb + t0 + 16 + m] : REC_NONE;
+    bool valid = have && j < lim;
+    if (valid && lb < le) {  // binary search in the row's sorted labels
+      int64_t lo = lb, hiq = le;
+      while (lo < hiq) {
+        const int64_t mid = (lo + hiq) >> 1;
+        if (g.lcol[mid] < j) lo = mid + 1;
+        else hiq = mid;
+      }
+      if (lo < le && g.lcol[lo] == j) valid = false;
+    }
+    double v = REC_NEG_INF;
+    if (cold) {
+      if (valid) v = g.popular[j];
+    } else {
+      V bq[RR_NA];
+#pragma unroll
+      for (int c = 0; c < RR_NA; c++) {
+        const int d = 16 * c + 4 * q;
+        const bool in = d < depth && valid;
+        const int tb = d < depth ? d / KP : 0, el = d % KP;
+        bq[c] = in ? M::ld(g.Q[tb] + (uint64_t)j * KP + el) : zero;
+      }
+      V acc = zero;
+#pragma unroll
+      for (int c = 0; c < RR_NA; c++)
+        if (c < nch) {
+#pragma unroll
+          for (int s = 0; s < 4; s++) acc = M::mma(aq[c][s], bq[c][s], acc);
+        }
+      for (int c = RR_NA; c < nch; c++) {
+        const int d = 16 * c + 4 * q;
+        const bool in = d < depth;
+        const int tb = in ? d / KP : 0, el = d % KP;
+        const V av = in ? M::ld(g.P[tb] + i * KP + el) : zero;
+        const V bv = (in && valid) ? M::ld(g.Q[tb] + (uint64_t)j * KP + el) : zero;
+#pragma unroll
+        for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
+      }
+      if (valid) v = (double)((acc[0] + g.b[j]) + ai);
+    }
+    const bool cand = valid && q == 0 && rec_better(v, j, tv, tj);
+    rerank_offer(__ballot(cand), v, j, v0, j0, v1, j1, tv, tj, g.topn, lane);
+  }
+  const bool whole = g.wptr[i + 1] - g.wptr[i] == 1;  // the row's only work item: its list is the result
+  double *dv = whole ? g.out_v + (i - g.r0) * (uint64_t)g.topn : g.part_v + wl * (uint64_t)g.topn;
+  uint32_t *dj = whole ? g.out_j + (i - g.r0) * (uint64_t)g.topn : g.part_j + wl * (uint64_t)g.topn;
+  if (lane < g.topn) {
+    dv[lane] = v0;
+    dj[lane] = j0;
+  }
+  if (lane + 64 < g.topn) {
+    dv[lane + 64] = v1;
+    dj[lane + 64] = j1;
+  }
+}
+
+// The partial lists of a row's work items merged into its result: one wave
+// per row offers every entry, in work item order, to one list (rerank_offer:
+// a copy counts once).  A row with one work item already has its result; a
+// row with none gets OCFFM_REC_NONE and -inf.
+static __global__ __launch_bounds__(BLOCK) void k_rerank_merge(uint64_t R, uint64_t r0, uint64_t w0, int topn,
+                                                               const int64_t *__restrict__ wptr,
+                                                               const double *__restrict__ part_v,
+                                                               const uint32_t *__restrict__ part_j,
+                                                               uint32_t *__restrict__ items,
+                                                               double *__restrict__ scores) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t il = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+  if (il >= R) return;  // (wave-uniform)
+  const int64_t wb = wptr[r0 + il], we = wptr[r0 + il + 1];
+  if (we - wb == 1) return;
+  double v0 = REC_NEG_INF, v1 = REC_NEG_INF, tv = REC_NEG_INF;
+  uint32_t j0 = REC_NONE, j1 = REC_NONE, tj = REC_NONE;
+  const uint64_t eb = (uint64_t)(wb - (int64_t)w0) * topn, ee = (uint64_t)(we - (int64_t)w0) * topn;
+  for (uint64_t e0 = eb; e0 < ee; e0 += 64) {
+    const bool have = e0 + lane < ee;
+    const uint32_t j = have ? part_j[e0 + lane] : REC_NONE;
+    const double v = have ? part_v[e0 + lane] : REC_NEG_INF;
+    const bool cand = j != REC_NONE && rec_better(v, j, tv, tj);
+    rerank_offer(__ballot(cand), v, j, v0, j0, v1, j1, tv, tj, topn, lane);
+  }
+  if (lane < topn) {
+    scores[il * topn + lane] = v0;
+    items[il * topn + lane] = j0;
+  }
+  if (lane + 64 < topn) {
+    scores[il * topn + lane + 64] = v1;
+    items[il * topn + lane + 64] = j1;
+  }
+}
+
 }  // namespace ocffm

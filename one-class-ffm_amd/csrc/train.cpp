@@ -11,6 +11,9 @@
 //   --recommend <file> --topn <n> --rec-out <path> [--rec-unseen]: after the
 //   solve (and any model save) the top-n items of every row of <file> (read
 //   like a -p file) go to <path>, one line of item:score tokens per row;
+//   with --rec-candidates <file> (line i: the whitespace-separated item
+//   indices row i is ranked among; a blank line is an empty list) the top-n
+//   of every row's own list instead;
 //   --eval <file> [--eval-cuts c1,c2,...] [--eval-seen <file>]: after that,
 //   the ranking metrics of the model on the labelled rows of <file> (read
 //   like a -p file) as one `eval` table on stdout.
@@ -19,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <stdexcept>
 #include <string>
@@ -46,6 +50,8 @@ static std::string usage() {
          "--topn <n>: items per row, 1..128 (default 10)\n"
          "--rec-out <path>: where the recommendations go (one line of item:score per row)\n"
          "--rec-unseen: leave out each row's own labels\n"
+         "--rec-candidates <path>: rank every row among its own list only (line i: the item indices of row i of\n"
+         "                         the --recommend file, whitespace-separated; a blank line is an empty list)\n"
          "--eval <path>: after training, print ranking metrics on the labelled rows of this file (read like -p)\n"
          "--eval-cuts <c1,c2,...>: up to 8 increasing cut-offs (default 5,10,20,40,80)\n"
          "--eval-seen <path>: rows whose labels are left out of the candidates (same row count as --eval)\n";
@@ -56,6 +62,36 @@ static bool is_numerical(const char *s) {
   for (; *s; s++)
     if (std::isdigit((unsigned char)*s)) return true;
   return false;
+}
+
+// --rec-candidates: one list per line.  Throws std::invalid_argument (exit 1).
+static void read_candidates(const std::string &path, std::uint64_t rows, std::vector<std::uint64_t> &cptr,
+                            std::vector<std::uint32_t> &ccol) {
+  std::ifstream in(path);
+  if (!in) throw std::invalid_argument("cannot read " + path);
+  cptr.assign(1, 0);
+  std::string line;
+  while (std::getline(in, line)) {
+    const char *s = line.c_str();
+    for (;;) {
+      while (*s && std::isspace((unsigned char)*s)) s++;
+      if (!*s) break;
+      const char *b = s;
+      std::uint64_t v = 0;
+      for (; std::isdigit((unsigned char)*s); s++) {
+        v = v * 10 + (std::uint64_t)(*s - '0');
+        if (v > 0xffffffffull) v = 0xffffffffull;  // (no item: OCFFM_REC_NONE is never a candidate)
+      }
+      if (s == b || (*s && !std::isspace((unsigned char)*s)))
+        throw std::invalid_argument(path + ": line " + std::to_string(cptr.size()) +
+                                    ": an item index must be a non-negative integer");
+      ccol.push_back((std::uint32_t)v);
+    }
+    cptr.push_back(ccol.size());
+  }
+  if (cptr.size() - 1 != rows)
+    throw std::invalid_argument(path + ": " + std::to_string(cptr.size() - 1) + " lines for " + std::to_string(rows) +
+                                " rows of the --recommend file");
 }
 
 struct Fail : std::runtime_error {
@@ -70,7 +106,7 @@ static void check(int st) {
 int main(int argc, char **argv) {
   ocffm_param prm;
   ocffm_param_default(&prm);
-  std::string te_path, model_path, rec_path, rec_out, eval_path, eval_seen;
+  std::string te_path, model_path, rec_path, rec_out, rec_cand, eval_path, eval_seen;
   std::vector<uint32_t> eval_cuts{5, 10, 20, 40, 80};
   long topn = 10;
   bool rec_unseen = false;
@@ -102,6 +138,7 @@ int main(int argc, char **argv) {
       else if (a == "--rec-out") rec_out = value(false, "need to specify path after --rec-out");
       else if (a == "--topn") topn = std::atol(value(true, "need to specify the number of items after --topn"));
       else if (a == "--rec-unseen") rec_unseen = true;
+      else if (a == "--rec-candidates") rec_cand = value(false, "need to specify path after --rec-candidates");
       else if (a == "--eval") eval_path = value(false, "need to specify path after --eval");
       else if (a == "--eval-seen") eval_seen = value(false, "need to specify path after --eval-seen");
       else if (a == "--eval-cuts") {
@@ -117,6 +154,7 @@ int main(int argc, char **argv) {
       else break;
     }
     if (!rec_path.empty() && rec_out.empty()) throw std::invalid_argument("--recommend needs --rec-out <path>");
+    if (!rec_cand.empty() && rec_path.empty()) throw std::invalid_argument("--rec-candidates needs --recommend <path>");
     if (topn < 1 || topn > OCFFM_REC_MAX_TOPN) throw std::invalid_argument("--topn must be in 1..128");
     if (!eval_seen.empty() && eval_path.empty()) throw std::invalid_argument("--eval-seen needs --eval <path>");
     if (eval_cuts.empty() || eval_cuts.size() > OCFFM_EVAL_MAX_CUTS) throw std::invalid_argument("--eval-cuts takes 1..8 cut-offs");
@@ -146,6 +184,20 @@ int main(int argc, char **argv) {
       check(ocffm_data_read(te_path.c_str(), 1, ds, (uint32_t)info.f, &Ut));
       delete[] ds;
     }
+    // the candidate lists are read and checked before any device work
+    ocffm_data *Xrec = nullptr;
+    std::vector<std::uint64_t> cptr;
+    std::vector<std::uint32_t> ccol;
+    if (!rec_cand.empty()) {
+      ocffm_data_info info, xi;
+      check(ocffm_data_get_info(U, &info));
+      std::vector<std::uint64_t> ds(info.f ? info.f : 1);
+      check(ocffm_data_get_ds(U, ds.data()));
+      check(ocffm_data_read(rec_path.c_str(), 1, ds.data(), (uint32_t)info.f, &Xrec));
+      check(ocffm_data_get_info(Xrec, &xi));
+      read_candidates(rec_cand, xi.m, cptr, ccol);
+      ccol.push_back(0);  // (a pointer for an empty file)
+    }
     phase("read");
     ocffm_problem *prob = nullptr;
     check(ocffm_problem_create(U, Ut, V, &prm, &prob));
@@ -166,14 +218,19 @@ int main(int argc, char **argv) {
       check(ocffm_data_get_info(U, &info));
       std::vector<std::uint64_t> ds(info.f ? info.f : 1);
       check(ocffm_data_get_ds(U, ds.data()));
-      ocffm_data *X = nullptr;
-      check(ocffm_data_read(rec_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
+      ocffm_data *X = Xrec;
+      if (!X) check(ocffm_data_read(rec_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
       ocffm_data_info xi;
       check(ocffm_data_get_info(X, &xi));
       std::vector<uint32_t> items(xi.m * (size_t)topn + 1);
       std::vector<double> scores(xi.m * (size_t)topn + 1);
-      check(ocffm_problem_recommend(prob, X, 0, xi.m, (uint32_t)topn, rec_unseen ? OCFFM_REC_EXCLUDE_LABELS : 0u,
-                                    items.data(), scores.data()));
+      const uint32_t flags = rec_unseen ? OCFFM_REC_EXCLUDE_LABELS : 0u;
+      if (rec_cand.empty()) {
+        check(ocffm_problem_recommend(prob, X, 0, xi.m, (uint32_t)topn, flags, items.data(), scores.data()));
+      } else {
+        check(ocffm_problem_recommend_among(prob, X, 0, xi.m, cptr.data(), ccol.data(), (uint32_t)topn, flags,
+                                            items.data(), scores.data()));
+      }
       std::FILE *fp = std::fopen(rec_out.c_str(), "w");
       if (!fp) throw Fail(OCFFM_E_IO, "cannot write " + rec_out);
       for (std::uint64_t i = 0; i < xi.m; i++) {

@@ -85,6 +85,7 @@ EXPORTS = [
     "ocffm_problem_set", "ocffm_problem_grad", "ocffm_problem_hv", "ocffm_problem_save_model",
     "ocffm_problem_validate_forced", "ocffm_problem_test_rows", "ocffm_problem_save_binary", "ocffm_problem_load_binary",
     "ocffm_problem_recommend", "ocffm_problem_label_ranks", "ocffm_eval_from_ranks", "ocffm_problem_evaluate",
+    "ocffm_problem_score", "ocffm_problem_recommend_among",
     "ocffm_problem_cg_log", "ocffm_problem_set_profiling", "ocffm_problem_set_profile_filter",
     "ocffm_problem_kernel_stats",
     "ocffm_problem_reset_stats", "ocffm_problem_alg_bytes", "ocffm_problem_counter", "ocffm_problem_sync",
@@ -137,6 +138,8 @@ def lib():
     L.ocffm_problem_test_rows.argtypes = [vp, C.POINTER(u64)]
     L.ocffm_problem_recommend.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp]
     L.ocffm_problem_label_ranks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ocffm_problem_score.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.ocffm_problem_recommend_among.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
     L.ocffm_eval_from_ranks.argtypes = [u64, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_problem_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_problem_save_binary.argtypes = [vp, C.c_char_p]
@@ -456,21 +459,51 @@ class ImpProblem:
         return dict(loss=m.loss, prec=np.array(m.prec[:]), ndcg=np.array(m.ndcg[:])), rows[:mt * 5].reshape(mt, 5)
 
     def recommend(self, X: ImpData, topn: int = 10, exclude_labels: bool = False, row0: int = 0,
-                  rows: Optional[int] = None):
+                  rows: Optional[int] = None, candidates=None):
         """Top-``topn`` items of rows [row0, row0 + rows) of ``X`` (default: to its
         end) under the current model (include/ocffm.h ocffm_problem_recommend):
         ``(items uint32 [rows, topn], scores float64 [rows, topn])``, score
         descending, equal scores by ascending item; unfilled slots hold
-        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels."""
+        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels.
+        With ``candidates=(cptr, ccol)`` each row is ranked among its own list
+        only (ocffm_problem_recommend_among): row ``row0 + i``'s list is
+        ``ccol[cptr[i]:cptr[i + 1]]``, ``cptr`` holding ``rows + 1`` offsets."""
         if rows is None:
             rows = max(0, int(X.info["m"]) - row0)
         shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
         items = np.full(shape, REC_NONE, dtype=np.uint32)
         scores = np.full(shape, -np.inf, dtype=np.float64)
-        _check(lib().ocffm_problem_recommend(self.h, X.h, row0, rows, topn,
-                                             REC_EXCLUDE_LABELS if exclude_labels else 0,
-                                             items.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
+        flags = REC_EXCLUDE_LABELS if exclude_labels else 0
+        if candidates is None:
+            _check(lib().ocffm_problem_recommend(self.h, X.h, row0, rows, topn, flags,
+                                                 items.ctypes.data_as(C.c_void_p),
+                                                 scores.ctypes.data_as(C.c_void_p)))
+            return items, scores
+        cptr = np.ascontiguousarray(candidates[0], dtype=np.uint64).reshape(-1)
+        ccol = np.ascontiguousarray(candidates[1], dtype=np.uint32).reshape(-1)
+        if cptr.size != rows + 1 or int(cptr.max()) > ccol.size:
+            raise OcffmError(E_ARG, "candidates: cptr needs rows + 1 offsets into ccol")
+        pad = np.zeros(1, dtype=np.uint32)  # (a pointer for an empty ccol)
+        _check(lib().ocffm_problem_recommend_among(self.h, X.h, row0, rows, _ptr(cptr),
+                                                   _ptr(ccol if ccol.size else pad), topn, flags,
+                                                   items.ctypes.data_as(C.c_void_p),
+                                                   scores.ctypes.data_as(C.c_void_p)))
         return items, scores
+
+    def score(self, X: ImpData, rows, items) -> np.ndarray:
+        """Scores of the pairs (row ``rows[e]`` of ``X``, item ``items[e]``) under
+        the current model (include/ocffm.h ocffm_problem_score): float64
+        [npairs], the values ``recommend`` returns for those pairs bit for bit;
+        ``-inf`` for an item that is no candidate of its row."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        j = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1)
+        if r.size != j.size:
+            raise OcffmError(E_ARG, "score: rows and items differ in length")
+        out = np.full(max(1, r.size), -np.inf, dtype=np.float64)
+        pad = np.zeros(1, dtype=np.uint32)
+        _check(lib().ocffm_problem_score(self.h, X.h, r.size, _ptr(r if r.size else pad), _ptr(j if j.size else pad),
+                                         _ptr(out)))
+        return out[: r.size]
 
     def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None):
         """Exact rank of every label of ``X`` among its row's candidates
