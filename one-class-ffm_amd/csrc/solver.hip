@@ -37,6 +37,7 @@
 #include "devbuild.h"
 #include "host_data.h"
 #include "kernels.hpp"
+#include "rank_kernels.hpp"
 
 namespace ocffm {
 
@@ -1099,6 +1100,90 @@ template <typename real> class Problem final : public ProblemBase {
     L.dlptr.upload(L.lptr);
     L.dlcol.upload(L.lcol);
   }
+  // The top-N calls' common arguments
+  void rec_check_topn(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, const uint32_t *items) {
+    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
+    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
+    if (!items) throw Error(OCFFM_E_ARG, "null items");
+  }
+  // Resident blocks of a kernel with a KP parameter (kernel_of(K): its instantiation)
+  template <class KOf> unsigned rec_resident(KOf &&kernel_of) {
+    unsigned slots = 0;
+    with_kp(kp_, [&](auto K) { slots = resident(kernel_of(K), 0); });
+    return slots;
+  }
+  uint64_t rec_chunk(uint64_t rows) const { return std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096); }
+  // Row chunk and item slices of a sweep (k_rec_topn, k_eval_count)
+  struct RecPlan {
+    uint64_t chunk, S, per;  // rows per launch; item slices; items per slice (multiple of REC_IT)
+  };
+  template <class KOf> RecPlan rec_plan(uint64_t rows, KOf &&kernel_of) {
+    RecPlan p;
+    p.chunk = rec_chunk(rows);
+    p.S = rec_slices_;
+    if (!p.S) {
+      // one resident wave of blocks: every slice costs each row its own
+      // list warm-up (~topn inserts), so as few slices as fill the machine;
+      // at least 4 item tiles per slice
+      p.S = std::max<uint64_t>(1, rec_resident(kernel_of) / ((p.chunk + REC_RT - 1) / REC_RT));
+      p.S = std::min<uint64_t>(p.S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
+      p.S = std::clamp<uint64_t>(p.S, 1, 64);
+    }
+    p.per = ((n_ + p.S - 1) / p.S + REC_IT - 1) / REC_IT * REC_IT;
+    return p;
+  }
+  // A sweep's arguments for rows [c0, c0 + cr) of L
+  void rec_sweep_args(SweepArgs<real> &g, const RecRows &L, uint64_t c0, uint64_t cr, const RecPlan &p, bool exclude) {
+    g.R = cr;
+    g.p0 = c0;
+    g.n = n_;
+    g.npop = std::min<uint64_t>(npop_, n_);
+    g.per = p.per;
+    g.C = (int)C_;
+    g.exclude = exclude ? 1 : 0;
+    g.S = (uint32_t)p.S;
+    g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
+    g.P = L.pt.p;
+    g.Q = tabs_.p + C_;
+    g.a = L.ax.p + c0;
+    g.b = V_.bias.p;
+    g.cold = L.dcold.p + c0;
+    g.popular = popular_.p;
+    g.lptr = L.dlptr.p + c0;
+    g.lcol = L.dlcol.p;
+  }
+  // Scores of the pairs (krow[e] of L, kitem[e]), every one a candidate, timed under `family`
+  std::vector<double> score_pairs(const RecRows &L, const std::vector<uint32_t> &krow,
+                                  const std::vector<uint32_t> &kitem, const char *family) {
+    const uint64_t nk = kitem.size();
+    DevBuf<uint32_t> dkrow, dkitem;
+    DevBuf<double> dkv;
+    dkrow.upload(krow);
+    dkitem.upload(kitem);
+    dkv.alloc(nk, false);
+    const double depth = (double)C_ * kp_;
+    prof_launch(family, (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
+      with_kp(kp_, [&](auto K) {
+        constexpr int KP = decltype(K)::value;
+        launch(k_eval_label_scores<real, KP>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)C_,
+               (const real *const *)L.pt.p, (const real *const *)(tabs_.p + C_), (const real *)L.ax.p,
+               (const real *)V_.bias.p, (const uint8_t *)L.dcold.p, (const double *)popular_.p,
+               (const uint32_t *)dkrow.p, (const uint32_t *)dkitem.p, dkv.p);
+      });
+    }, 2.0 * (double)nk * depth);
+    std::vector<double> kv(nk);
+    HIPCHK(hipMemcpyAsync(kv.data(), dkv.p, nk * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    sync();
+    return kv;
+  }
+  // A chunk's results (rows c0.. of the call) to the caller's arrays
+  void rec_copy_back(uint64_t c0, uint64_t cr, uint32_t topn, const DevBuf<uint32_t> &out_j, const DevBuf<double> &out_v,
+                     uint32_t *items, double *scores) {
+    HIPCHK(hipMemcpyAsync(items + c0 * topn, out_j.p, cr * topn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+    if (scores)
+      HIPCHK(hipMemcpyAsync(scores + c0 * topn, out_v.p, cr * topn * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    sync();
+  }
 
   // ------------------------------------------------- ranking evaluation
   // Exact rank of every label of X among its row's candidates (ocffm.h
@@ -1161,43 +1246,18 @@ template <typename real> class Problem final : public ProblemBase {
           (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
       return;
     }
-    DevBuf<uint32_t> dkrow, dkitem, dcnt;
+    DevBuf<uint32_t> dcnt;
     DevBuf<int64_t> dkptr;
-    DevBuf<double> dkv;
-    dkrow.upload(krow);
-    dkitem.upload(kitem);
     dkptr.upload(kptr);
-    dkv.alloc(nk, false);
     dcnt.alloc(nk);
-    // chunking and slicing (recommend's, with this kernel's residency)
-    const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
-    const uint64_t rt = (chunk + REC_RT - 1) / REC_RT;
-    uint64_t S = rec_slices_;
-    if (!S) {
-      unsigned slots = 2 * ncu_;
-      with_kp(kp_, [&](auto K) { slots = resident(k_eval_count<real, decltype(K)::value>, 0); });
-      S = std::max<uint64_t>(1, slots / rt);
-      S = std::min<uint64_t>(S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
-      S = std::clamp<uint64_t>(S, 1, 64);
-    }
-    const uint64_t per = ((n_ + S - 1) / S + REC_IT - 1) / REC_IT * REC_IT;
+    const RecPlan plan = rec_plan(rows, [](auto K) { return k_eval_count<real, decltype(K)::value>; });
+    const uint64_t chunk = plan.chunk;
     sync();
     counters["eval_setup_us"] =
         (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
     const double depth = (double)C_ * kp_;
     // the labels' own scores
-    prof_launch("evaluate", (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
-      with_kp(kp_, [&](auto K) {
-        constexpr int KP = decltype(K)::value;
-        launch(k_eval_label_scores<real, KP>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)C_,
-               (const real *const *)L.pt.p, (const real *const *)(tabs_.p + C_), (const real *)L.ax.p,
-               (const real *)V_.bias.p, (const uint8_t *)L.dcold.p, (const double *)popular_.p,
-               (const uint32_t *)dkrow.p, (const uint32_t *)dkitem.p, dkv.p);
-      });
-    }, 2.0 * (double)nk * depth);
-    std::vector<double> kv(nk);
-    HIPCHK(hipMemcpyAsync(kv.data(), dkv.p, nk * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    sync();
+    const std::vector<double> kv = score_pairs(L, krow, kitem, "evaluate");
     // each row's labels in ranking order
     std::vector<uint32_t> ord(nk);
     for (uint64_t e = 0; e < nk; e++) ord[e] = (uint32_t)e;
@@ -1219,23 +1279,7 @@ template <typename real> class Problem final : public ProblemBase {
       const uint64_t cr = std::min(chunk, rows - c0);
       if (kptr[c0 + cr] == kptr[c0]) continue;  // no label in these rows
       EvalArgs<real> g{};
-      g.R = cr;
-      g.p0 = c0;
-      g.n = n_;
-      g.npop = npop;
-      g.per = per;
-      g.C = (int)C_;
-      g.seen = seen ? 1 : 0;
-      g.S = (uint32_t)S;
-      g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
-      g.P = L.pt.p;
-      g.Q = tabs_.p + C_;
-      g.a = L.ax.p + c0;
-      g.b = V_.bias.p;
-      g.cold = L.dcold.p + c0;
-      g.popular = popular_.p;
-      g.sptr = L.dlptr.p + c0;
-      g.scol = L.dlcol.p;
+      rec_sweep_args(g, L, c0, cr, plan, seen != nullptr);
       g.kptr = dkptr.p + c0;
       g.kv = dsv.p;
       g.kj = dsj.p;
@@ -1278,9 +1322,7 @@ template <typename real> class Problem final : public ProblemBase {
   void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
                  double *scores) override {
     need_init();
-    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
-    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
-    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    rec_check_topn(X, row0, rows, topn, items);
     rec_check(X, row0, rows);
     if (rows == 0) return;
     sync_owned();
@@ -1289,26 +1331,8 @@ template <typename real> class Problem final : public ProblemBase {
     const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
     RecRows L;
     rec_layout(L, X, row0, rows, excl ? &X : nullptr);
-    DevBuf<real *> &pt = L.pt;
-    DevBuf<real> &ax = L.ax;
-    DevBuf<uint8_t> &dcold = L.dcold;
-    DevBuf<int64_t> &dlptr = L.dlptr;
-    DevBuf<uint32_t> &dlcol = L.dlcol;
-    // chunking and slicing
-    const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
-    const uint64_t rt = (chunk + REC_RT - 1) / REC_RT;
-    uint64_t S = rec_slices_;
-    if (!S) {
-      // one resident wave of blocks: every slice costs each row its own
-      // list warm-up (~topn inserts), so as few slices as fill the machine;
-      // at least 4 item tiles per slice
-      unsigned slots = 2 * ncu_;
-      with_kp(kp_, [&](auto K) { slots = resident(k_rec_topn<real, decltype(K)::value>, 0); });
-      S = std::max<uint64_t>(1, slots / rt);
-      S = std::min<uint64_t>(S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
-      S = std::clamp<uint64_t>(S, 1, 64);
-    }
-    const uint64_t per = ((n_ + S - 1) / S + REC_IT - 1) / REC_IT * REC_IT;
+    const RecPlan plan = rec_plan(rows, [](auto K) { return k_rec_topn<real, decltype(K)::value>; });
+    const uint64_t chunk = plan.chunk, S = plan.S;
     DevBuf<double> part_v, out_v;
     DevBuf<uint32_t> part_j, out_j;
     part_v.alloc(chunk * S * topn, false);
@@ -1321,24 +1345,8 @@ template <typename real> class Problem final : public ProblemBase {
     for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
       const uint64_t cr = std::min(chunk, rows - c0);
       RecArgs<real> g{};
-      g.R = cr;
-      g.p0 = c0;
-      g.n = n_;
-      g.npop = std::min<uint64_t>(npop_, n_);
-      g.per = per;
-      g.C = (int)C_;
-      g.S = (uint32_t)S;
-      g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
+      rec_sweep_args(g, L, c0, cr, plan, excl);
       g.topn = (int)topn;
-      g.exclude = excl ? 1 : 0;
-      g.P = pt.p;
-      g.Q = tabs_.p + C_;
-      g.a = ax.p + c0;
-      g.b = V_.bias.p;
-      g.cold = dcold.p + c0;
-      g.popular = popular_.p;
-      g.lptr = dlptr.p + c0;
-      g.lcol = dlcol.p;
       g.part_v = part_v.p;
       g.part_j = part_j.p;
       const double depth = (double)C_ * kp_;
@@ -1352,10 +1360,7 @@ template <typename real> class Problem final : public ProblemBase {
         launch(k_rec_merge, (unsigned)cr, BLOCK, 0, cr, (int)S, (int)topn, (const double *)part_v.p,
                (const uint32_t *)part_j.p, out_j.p, out_v.p);
       }, 2.0 * (double)cr * (double)n_ * depth);
-      HIPCHK(hipMemcpyAsync(items + c0 * topn, out_j.p, cr * topn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-      if (scores)
-        HIPCHK(hipMemcpyAsync(scores + c0 * topn, out_v.p, cr * topn * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      sync();
+      rec_copy_back(c0, cr, topn, out_j, out_v, items, scores);
     }
     flush_prof();
   }
@@ -1386,31 +1391,13 @@ template <typename real> class Problem final : public ProblemBase {
       kitem.push_back(pitem[e]);
       where.push_back(e);
     }
-    const uint64_t nk = kitem.size();
-    DevBuf<uint32_t> dkrow, dkitem;
-    DevBuf<double> dkv;
-    dkrow.upload(krow);
-    dkitem.upload(kitem);
-    dkv.alloc(nk, false);
     sync();
     counters["rec_setup_us"] =
         (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
-    if (nk == 0) return;
-    const double depth = (double)C_ * kp_;
-    prof_launch("rerank", (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
-      with_kp(kp_, [&](auto K) {
-        constexpr int KP = decltype(K)::value;
-        launch(k_eval_label_scores<real, KP>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)C_,
-               (const real *const *)L.pt.p, (const real *const *)(tabs_.p + C_), (const real *)L.ax.p,
-               (const real *)V_.bias.p, (const uint8_t *)L.dcold.p, (const double *)popular_.p,
-               (const uint32_t *)dkrow.p, (const uint32_t *)dkitem.p, dkv.p);
-      });
-    }, 2.0 * (double)nk * depth);
-    std::vector<double> kv(nk);
-    HIPCHK(hipMemcpyAsync(kv.data(), dkv.p, nk * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    sync();
+    if (kitem.empty()) return;
+    const std::vector<double> kv = score_pairs(L, krow, kitem, "rerank");
     flush_prof();
-    for (uint64_t t = 0; t < nk; t++) out[where[t]] = kv[t];
+    for (size_t t = 0; t < kv.size(); t++) out[where[t]] = kv[t];
   }
 
   // ------------------------------------------ top-N among candidate lists
@@ -1431,9 +1418,7 @@ template <typename real> class Problem final : public ProblemBase {
   void recommend_among(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol,
                        uint32_t topn, uint32_t flags, uint32_t *items, double *scores) override {
     need_init();
-    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
-    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
-    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    rec_check_topn(X, row0, rows, topn, items);
     if (!cptr) throw Error(OCFFM_E_ARG, "null cptr");
     if (cptr[0] != 0) throw Error(OCFFM_E_ARG, "cptr[0] must be 0");
     for (uint64_t i = 0; i < rows; i++)
@@ -1450,8 +1435,7 @@ template <typename real> class Problem final : public ProblemBase {
     // work items: row-major, a row's segments in list order
     uint64_t seg = rec_seg_;
     if (!seg) {
-      unsigned slots = 2 * ncu_;
-      with_kp(kp_, [&](auto K) { slots = resident(k_rerank<real, decltype(K)::value>, 0); });
+      const unsigned slots = rec_resident([](auto K) { return k_rerank<real, decltype(K)::value>; });
       seg = cptr[rows] / ((uint64_t)slots * (BLOCK / 64)) + 1;
       seg = (std::clamp(seg, REC_SEG_MIN, REC_SEG_MAX) + 15) / 16 * 16;
     }
@@ -1466,7 +1450,7 @@ template <typename real> class Problem final : public ProblemBase {
       }
       wptr[i + 1] = (int64_t)wrow.size();
     }
-    const uint64_t chunk = std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096);
+    const uint64_t chunk = rec_chunk(rows);
     uint64_t maxw = 0, maxc = 0;
     for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
       const uint64_t c1 = std::min(rows, c0 + chunk);
@@ -1541,10 +1525,7 @@ template <typename real> class Problem final : public ProblemBase {
         launch(k_rerank_merge, (unsigned)((cr + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, cr, c0, g.w0, (int)topn,
                (const int64_t *)dwptr.p, (const double *)part_v.p, (const uint32_t *)part_j.p, out_j.p, out_v.p);
       }, 2.0 * (double)nc * depth);
-      HIPCHK(hipMemcpyAsync(items + c0 * topn, out_j.p, cr * topn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-      if (scores)
-        HIPCHK(hipMemcpyAsync(scores + c0 * topn, out_v.p, cr * topn * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      sync();
+      rec_copy_back(c0, cr, topn, out_j, out_v, items, scores);
     }
     flush_prof();
   }

@@ -191,7 +191,7 @@ def test_parity_ragged_shapes(k, precision):
     pop = popularity(g._keep[0])
     tol = tol_for(precision, ref)
     none = excluded_sets(X, n, False)
-    for topn in (1, 10, 128):
+    for topn in (1, 10, 64, 65, 128):
         items, scores = g.recommend(X, topn=topn)
         assert items.dtype == np.uint32 and items.shape == (37, topn)
         assert_topn(items, scores, ref, tol, none)

@@ -166,7 +166,7 @@ def test_full_lists_reproduce_recommend(precision, exclude):
     X = g._keep[1]
     rng = np.random.default_rng(3)
     cptr, ccol = lists_of([rng.permutation(N).tolist() for _ in range(ROWS)])
-    for topn in (1, 10, 70, 128):
+    for topn in (1, 10, 64, 65, 70, 128):
         want = g.recommend(X, topn=topn, exclude_labels=exclude)
         got = g.recommend(X, topn=topn, exclude_labels=exclude, candidates=(cptr, ccol))
         assert got[0].dtype == np.uint32 and got[0].shape == (ROWS, topn)
