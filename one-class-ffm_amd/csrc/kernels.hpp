@@ -1497,6 +1497,11 @@ __global__ __launch_bounds__(BLOCK) void k_hs_side_row(uint64_t R, const int64_t
 // 256-row chunks 44 us, 128 rows 32 us (default), 64 rows 34 us per build.
 constexpr int cgram_rows(int kp, int rs) { return 32768 / (kp * rs) < 256 ? 32768 / (kp * rs) : 256; }
 
+// The VALU build of the side column and pair Grams (every KP but 32, and
+// OCFFM_NO_MFMA; else k_gram_build_mfma with WtHess below).  It keeps its
+// in-kernel sum of multi-chunk columns: the slot-sum launch of the other
+// builds measured + 4 us per build at the kdd12 shape (k = 16: 23.6 -> 27.5
+// us fp32, 35.7 -> 40.2 us fp64, profiles/gram_refactor_ab.json).
 // One block per chunk (Job: col, nparts = chunks of the column, slot =
 // partial slot, flags = chunk index in the column, [b, e) in the field's
 // CSC, e - b <= cgram_rows): each thread sums its entries of the chunk's
@@ -1595,143 +1600,6 @@ __global__ __launch_bounds__(BLOCK) void k_col_gram(const Job *__restrict__ chun
   if (threadIdx.x == 0) __hip_atomic_store(cnt + jb.col, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Per-column Grams on MFMA (fp32, KP = 32; the default where it applies).
-// One WAVE per chunk of <= CGRAM32_ROWS rows of a column: lane l stages row
-// l's index and weight c_l = d_i x_i^2, then each v_mfma_f32_32x32x2f32 takes
-// a row pair r = 2s + l/32 (A lane l = c_r q_r[l%32], B lane l = q_r[l%32],
-// the k_gram_mfma32 operand layout): the chunk's sum_r c_r q_r q_r^T builds
-// up in 16 accumulator registers with no LDS.  Every q-row load of the
-// chunk is issued before the first MFMA (one latency round).  A one-chunk
-// column stores G_c; the chunks of a longer column store their partial
-// slot (plain stores) and k_gram_slot_sum adds the slots in slot order after
-// the launch (deterministic; no tickets, no in-kernel hand-off).  Replaces
-// k_col_gram's one block per <= 128-row chunk, whose rank-1 updates read two
-// LDS words per multiply-add (genre: 32.7 us, artist: 35.4 us per build).
-constexpr int CGRAM32_ROWS = 64;
-static __global__ __launch_bounds__(BLOCK) void k_col_gram32(uint64_t nchunks, const Job *__restrict__ chunks,
-                                                      const uint32_t *__restrict__ crow,
-                                                      const float *__restrict__ cval, const int64_t *__restrict__ yptr,
-                                                      const float *__restrict__ Q1, uint64_t q1rows, double w, double n1,
-                                                      float *__restrict__ G, float *__restrict__ gpart, int pw) {
-  typedef float f16x __attribute__((ext_vector_type(16)));
-  const int lane = threadIdx.x & 63;
-  const uint64_t wv = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  if (wv >= nchunks) return;
-  const Job jb = chunks[wv];
-  const int n = (int)(jb.e - jb.b);  // <= CGRAM32_ROWS (host)
-  uint32_t il = 0;
-  float cl = 0.0f;
-  if (lane < n) {
-    il = crow[jb.b + lane];
-    const float x = cval[jb.b + lane];
-    cl = (float)((1 - w) * (double)(yptr[il + 1] - yptr[il]) + w * n1) * (pw ? x : x * x);
-  }
-  const BufView qb = buf_view(Q1, q1rows * 128);
-  const int e = lane & 31, hf = lane >> 5;
-  float qv[CGRAM32_ROWS / 2], cv[CGRAM32_ROWS / 2];
-#pragma unroll
-  for (int s = 0; s < CGRAM32_ROWS / 2; s++) {
-    const int r = 2 * s + hf;  // rows past n: weight 0, the load reads zero
-    const uint32_t i = (uint32_t)__shfl((int)il, r, 64);
-    cv[s] = __shfl(cl, r, 64);
-    qv[s] = bld1<float>(qb, r < n ? i * 128u + (uint32_t)e * 4u : 0xffffffffu);
-  }
-  f16x acc;
-#pragma unroll
-  for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-  // branch-free (rows past n have weight and row zero): a per-MFMA branch
-  // made the compiler copy the accumulator between AGPRs and VGPRs each time
-#pragma unroll
-  for (int s = 0; s < CGRAM32_ROWS / 2; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[s] * qv[s], qv[s], acc, 0, 0, 0);
-  // D register r of lane l: element m = 8(r/4) + 4(l/32) + r%4, n = l%32
-  float *out = jb.nparts <= 1 ? G + (size_t)jb.col * 1024 : gpart + (size_t)jb.slot * 1024;
-#pragma unroll
-  for (int r = 0; r < 16; r++) out[(8 * (r >> 2) + 4 * hf + (r & 3)) * 32 + e] = acc[r];
-}
-
-// The same in fp64 on the f64 matrix cores (v_mfma_f64_16x16x4f64, the
-// k_hot_gram_mfma_f64 operand layout: four rows per MFMA as K; tiles 00, 01,
-// 11 of the symmetric 32 x 32 Gram, 10 stored as 01^T); multi-chunk columns
-// summed by k_hot_slot_sum<double, 32>.
-static __global__ __launch_bounds__(BLOCK) void k_col_gram_f64(uint64_t nchunks, const Job *__restrict__ chunks,
-                                                              const uint32_t *__restrict__ crow,
-                                                              const double *__restrict__ cval,
-                                                              const int64_t *__restrict__ yptr,
-                                                              const double *__restrict__ Q1, uint64_t q1rows, double w,
-                                                              double n1, double *__restrict__ G,
-                                                              double *__restrict__ gpart, int pw) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  constexpr int NG = CGRAM32_ROWS / 4;
-  const int lane = threadIdx.x & 63;
-  const uint64_t wv = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  if (wv >= nchunks) return;
-  const Job jb = chunks[wv];
-  const int n = (int)(jb.e - jb.b);  // <= CGRAM32_ROWS (host)
-  uint32_t il = 0;
-  double cl = 0.0;
-  if (lane < n) {
-    il = crow[jb.b + lane];
-    const double x = cval[jb.b + lane];
-    cl = ((1 - w) * (double)(yptr[il + 1] - yptr[il]) + w * n1) * (pw ? x : x * x);
-  }
-  const BufView qb = buf_view(Q1, q1rows * 256);
-  const int c16 = lane & 15, rq = lane >> 4;
-  double q0[NG], q1[NG], cv[NG];
-#pragma unroll
-  for (int g = 0; g < NG; g++) {
-    const int r = 4 * g + rq;  // rows past n: weight 0, the loads read zero
-    const uint32_t i = (uint32_t)__shfl((int)il, r, 64);
-    cv[g] = __shfl(cl, r, 64);
-    const uint32_t off = r < n ? i * 256u + (uint32_t)c16 * 8u : 0xffffffffu;
-    q0[g] = bld1<double>(qb, off);
-    q1[g] = bld1<double>(qb, r < n ? off + 128u : 0xffffffffu);
-  }
-  d4 acc[2][3];
-#pragma unroll
-  for (int u = 0; u < 2; u++)
-#pragma unroll
-    for (int a = 0; a < 3; a++) acc[u][a] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int g = 0; g < NG; g++) {
-    d4(&c)[3] = acc[g & 1];
-    const double a0 = cv[g] * q0[g], a1 = cv[g] * q1[g];
-    c[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, q0[g], c[0], 0, 0, 0);
-    c[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, q1[g], c[1], 0, 0, 0);
-    c[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, q1[g], c[2], 0, 0, 0);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) acc[0][a] += acc[1][a];
-  double *out = jb.nparts <= 1 ? G + (size_t)jb.col * 1024 : gpart + (size_t)jb.slot * 1024;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = rq + 4 * r;
-    out[m * 32 + c16] = acc[0][0][r];
-    out[m * 32 + 16 + c16] = acc[0][1][r];
-    out[(16 + c16) * 32 + m] = acc[0][1][r];
-    out[(16 + m) * 32 + 16 + c16] = acc[0][2][r];
-  }
-}
-
-// G_c = sum of the partial slots of a multi-chunk column, in slot order
-// (sums: Job{col, nparts, first slot}).  One block per such column; thread t
-// owns elements 4t .. 4t+3; slots are read GB at a time (loads in flight).
-static __global__ __launch_bounds__(BLOCK) void k_gram_slot_sum(const Job *__restrict__ sums,
-                                                         const float *__restrict__ gpart, float *__restrict__ G) {
-  constexpr int GB = 8;
-  const Job jb = sums[blockIdx.x];
-  const f4v *src = reinterpret_cast<const f4v *>(gpart + (size_t)jb.slot * 1024) + threadIdx.x;
-  f4v acc = src[0];
-  for (uint32_t q0 = 1; q0 < jb.nparts; q0 += GB) {
-    f4v y[GB];
-#pragma unroll
-    for (int u = 0; u < GB; u++) y[u] = q0 + u < jb.nparts ? src[(size_t)(q0 + u) * 256] : f4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < GB; u++)
-      if (q0 + u < jb.nparts) acc += y[u];
-  }
-  reinterpret_cast<f4v *>(G + (size_t)jb.col * 1024)[threadIdx.x] = acc;
-}
-
 // ------------------------------------------- per-row Grams (cross) ---
 // Hot rows of a cross half: a row i with many positives has
 //   sum_{j in Omega_i} <phi_i, q_j> q_j = G_i phi_i,  G_i = sum_{j in Omega_i} q_j q_j^T
@@ -1741,7 +1609,7 @@ static __global__ __launch_bounds__(BLOCK) void k_gram_slot_sum(const Job *__res
 // popular item's ~10^4 users; a heavy user's ~10^2 items).  Chunks
 // (Job: col = the row's Gram slot, nparts = chunks of the row, slot = the
 // partial slot, [b, e) = a range of the row's positives) sum into G, or into
-// ordered partial slots that k_hot_slot_sum adds in slot order after the
+// ordered partial slots that k_gram_slot_sum adds in slot order after the
 // launch (deterministic).  HOT_NONE: a segment of a row without a Gram.
 constexpr uint32_t HOT_NONE = 0xffffffffu;
 
@@ -1752,14 +1620,45 @@ static __global__ __launch_bounds__(BLOCK) void k_hot_seg(uint64_t nseg, const S
   if (s < nseg) out[s] = row_slot[segs[s].row];
 }
 
-// Generic build (fp64, or any KP): one block per chunk, the chunk's partner
-// rows staged through LDS cgram_rows at a time, thread t owns elements
-// t, t + BLOCK, ... of the k x k sum.  wts (optional): a weight per position
-// (per-column cross Grams: x_i^2 of the position's row).
+// ------------------------------------- Gram builds from gathered rows ---
+// The per-column (side), per-pair, per-row (hot) and per-column cross Grams
+// are one operation over a list of chunk jobs (Job: col = the Gram, nparts =
+// chunks of the Gram, slot = the chunk's partial slot, flags = its index in
+// the Gram, [b, e) = a range of entries p with a row idx[p] of Q1):
+//   G[col] (or partial slot) = sum_{p in [b, e)} wt(p, idx[p]) q_idx[p] q_idx[p]^T
+// A one-chunk Gram is stored to G; the chunks of a longer one store their
+// partial slots (plain stores) and k_gram_slot_sum adds the slots in slot
+// order after the launch: deterministic, no float atomics, no tickets, no
+// in-kernel hand-off (k_col_gram above, the VALU build with Hessian weights,
+// alone keeps its own).  The weight policies wt(p, i) of entry p with row i:
+// a weight per entry or 1 (hot rows: 1; cross column Grams: (1 - w) x^2 of
+// the entry's row) ...
+template <typename real> struct WtList {
+  static constexpr bool column_tau = true;  // (the MFMA builds' xsq epilogue: compiled for these weights only)
+  const real *wts;
+  __device__ real operator()(int64_t p, uint32_t) const { return wts ? wts[p] : (real)1; }
+};
+// ... and the Hessian weight d_i x_p^2 of a side column Gram (pw: d_i x_p,
+// x_p = X_ia X_ib of a pair Gram's entry), d_i = (1 - w) |Omega_i| + w n1.
+template <typename real> struct WtHess {
+  static constexpr bool column_tau = false;
+  const real *cval;
+  const int64_t *yptr;
+  double w, n1;
+  int pw;
+  __device__ real operator()(int64_t p, uint32_t i) const {
+    const real x = cval[p];
+    return (real)((1 - w) * (double)(yptr[i + 1] - yptr[i]) + w * n1) * (pw ? x : x * x);
+  }
+};
+
+// Generic build with list weights (any precision and KP): one block per
+// chunk, the chunk's rows staged through LDS cgram_rows at a time, thread t
+// owns elements t, t + BLOCK, ... of the k x k sum.
 template <typename real, int KP>
-__global__ __launch_bounds__(BLOCK) void k_hot_gram(const Job *__restrict__ chunks, const uint32_t *__restrict__ ycol,
-                                                    const real *__restrict__ wts, const real *__restrict__ Q1,
-                                                    real *__restrict__ G, real *__restrict__ gpart) {
+__global__ __launch_bounds__(BLOCK) void k_gram_build(const Job *__restrict__ chunks, const uint32_t *__restrict__ idx,
+                                                      const real *__restrict__ wts, const real *__restrict__ Q1,
+                                                      real *__restrict__ G, real *__restrict__ gpart) {
   constexpr int CH = cgram_rows(KP, (int)sizeof(real));
   constexpr int KK = KP * KP;
   constexpr int NE = (KK + BLOCK - 1) / BLOCK;
@@ -1772,7 +1671,7 @@ __global__ __launch_bounds__(BLOCK) void k_hot_gram(const Job *__restrict__ chun
   for (int64_t b0 = jb.b; b0 < jb.e; b0 += CH) {
     const int n = (int)(jb.e - b0 < CH ? jb.e - b0 : CH);
     __syncthreads();
-    for (int t = threadIdx.x; t < n * KP; t += BLOCK) qs[t] = Q1[(size_t)ycol[b0 + t / KP] * KP + t % KP];
+    for (int t = threadIdx.x; t < n * KP; t += BLOCK) qs[t] = Q1[(size_t)idx[b0 + t / KP] * KP + t % KP];
     for (int t = threadIdx.x; t < n; t += BLOCK) ws[t] = wts ? wts[b0 + t] : (real)1;
     __syncthreads();
     for (int r = 0; r < n; r++) {
@@ -1792,34 +1691,38 @@ __global__ __launch_bounds__(BLOCK) void k_hot_gram(const Job *__restrict__ chun
   }
 }
 
-// fp32 builds on MFMA (v_mfma_f32_32x32x2f32, the k_col_gram32 operand
-// layout: a row pair r = 2s + lane/32 is the K dimension, lane l holds
-// w_r q_r[l % 32] as the A and q_r[l % 32] as the B operand).  One wave per
-// chunk (the host cuts a long row or column into up to 64 chunks, so a
-// popular item's ~10^4 positions spread over many waves); the chunk's rows
-// 32 at a time: one coalesced load of their indices and weights, the row
-// loads all in flight, then 16 MFMAs alternating over two accumulator sets.
-// Small batches keep the kernel at ~70 VGPRs (KP = 32), so several waves
-// per SIMD hide each other's load latency (a software-pipelined 64-row
-// version at 232 registers ran 3x slower).  KP = 32: one 32 x 32 tile.
-// KP = 64: tiles 00, 01 and 11 (G is symmetric; tile 10 is stored as the
-// transpose of 01).
+// The builds on MFMA: one WAVE per chunk, the chunk's rows HB at a time:
+// one coalesced load of their indices and weights, every row load of the
+// batch issued before its first MFMA (one latency round), then the MFMAs
+// alternating over NA accumulator sets, with no LDS.  xsq (optional; the
+// per-column cross Grams): the column tau w xsq_c QTQ, added once, by the
+// column's first chunk (the slot sum carries it).
+//   Hot rows and cross column Grams: HB = 32, NA = 2 (the host cuts a long
+// row or column into up to 64 chunks of ~HOT_CHUNK_MAX, so a popular item's
+// ~10^4 positions spread over many waves).  Small batches keep the kernel
+// at ~70 VGPRs (fp32, KP = 32), so several waves per SIMD hide each other's
+// load latency (a software-pipelined 64-row version at 232 registers ran 3x
+// slower).
+//   Side column and pair Grams: HB = GRAM_WAVE_ROWS = 64, the host's chunk
+// length there, so a chunk is one batch; NA = 1 (fp32), 2 (fp64).  Replaced
+// a block per <= 128-row chunk on k_col_gram, whose rank-1 updates read
+// two LDS words per multiply-add (genre: 32.7 us, artist: 35.4 us per build).
 constexpr int HOT_CHUNK_MAX = 256;
-template <int KP>
-__global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma(uint64_t nchunks, const Job *__restrict__ chunks,
-                                                         const uint32_t *__restrict__ ycol,
-                                                         const float *__restrict__ wts,
-                                                         const float *__restrict__ Q1, uint64_t q1rows,
-                                                         float *__restrict__ G, float *__restrict__ gpart,
-                                                         const float *__restrict__ xsq, const float *__restrict__ QTQ,
-                                                         float w) {
-  static_assert(KP == 32 || KP == 64, "MFMA hot Grams: KP 32 or 64");
+constexpr int GRAM_WAVE_ROWS = 64;
+
+// fp32 (v_mfma_f32_32x32x2f32, the k_gram_mfma32 operand layout): a row pair
+// r = 2s + lane/32 is the K dimension, lane l holds w_r q_r[l % 32] as the A
+// and q_r[l % 32] as the B operand.  KP = 32: one 32 x 32 tile.  KP = 64:
+// tiles 00, 01 and 11 (G is symmetric; tile 10 is stored as 01^T).
+template <int KP, int HB, int NA, class Wt>
+__device__ __forceinline__ void gram_chunk_mfma(const Job jb, const uint32_t *__restrict__ idx, const Wt wt,
+                                                const float *__restrict__ Q1, uint64_t q1rows, float *__restrict__ G,
+                                                float *__restrict__ gpart, const float *__restrict__ xsq,
+                                                const float *__restrict__ QTQ, float w) {
+  static_assert(KP == 32 || KP == 64, "fp32 MFMA Gram builds: KP 32 or 64");
   typedef float f16x __attribute__((ext_vector_type(16)));
-  constexpr int T = KP / 32, NT = T == 1 ? 1 : 3, NA = 2, HB = 32, NS = HB / 2;
+  constexpr int T = KP / 32, NT = T == 1 ? 1 : 3, NS = HB / 2;
   const int lane = threadIdx.x & 63;
-  const uint64_t wv = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  if (wv >= nchunks) return;
-  const Job jb = chunks[wv];
   const BufView qb = buf_view(Q1, q1rows * KP * 4);
   const int e = lane & 31, hf = lane >> 5;
   f16x acc[NA][NT];
@@ -1829,16 +1732,24 @@ __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma(uint64_t nchunks, const
     for (int a = 0; a < NT; a++)
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[u][a][r] = 0.0f;
-  for (int64_t b0 = jb.b; b0 < jb.e; b0 += HB) {
-    const int n = (int)(jb.e - b0 < HB ? jb.e - b0 : HB);
-    const uint32_t il = lane < n ? ycol[b0 + lane] : 0u;
-    const float wl = lane < n ? (wts ? wts[b0 + lane] : 1.0f) : 0.0f;
-    float q0[NS], q1[T == 1 ? 1 : NS], w[NS];
+  int64_t b0 = jb.b;
+  // HB = GRAM_WAVE_ROWS requires e - b <= HB (checked by the host, gram_launch):
+  // the chunk is one batch and the code has no loop, which keeps these
+  // instances at 8 (fp32) / 4 (fp64) waves per SIMD; with the loop 4 / 2.
+  do {  // (an empty chunk: one batch of zeros)
+    const int n = HB < GRAM_WAVE_ROWS ? (int)(jb.e - b0 < HB ? jb.e - b0 : HB) : (int)(jb.e - b0);
+    uint32_t il = 0u;
+    float wl = 0.0f;
+    if (lane < n) {  // (one block: the index and weight loads issued together)
+      il = idx[b0 + lane];
+      wl = wt(b0 + lane, il);
+    }
+    float q0[NS], q1[T == 1 ? 1 : NS], wr[NS];
 #pragma unroll
     for (int s = 0; s < NS; s++) {
       const int r = 2 * s + hf;  // rows past n read zero (buffer range check)
       const uint32_t i = (uint32_t)__shfl((int)il, r, 64);
-      w[s] = __shfl(wl, r, 64);
+      wr[s] = __shfl(wl, r, 64);
       const uint32_t off = r < n ? i * (uint32_t)(KP * 4) + (uint32_t)e * 4u : 0xffffffffu;
       q0[s] = bld1<float>(qb, off);
       if constexpr (T == 2) q1[s] = bld1<float>(qb, r < n ? off + 128u : 0xffffffffu);
@@ -1849,27 +1760,31 @@ __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma(uint64_t nchunks, const
 #pragma unroll
     for (int s = 0; s < NS; s++) {
       f16x(&c)[NT] = acc[s % NA];
-      const float a0 = w[s] * q0[s];
+      const float a0 = wr[s] * q0[s];
       c[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, q0[s], c[0], 0, 0, 0);
       if constexpr (T == 2) {
         c[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, q1[s], c[1], 0, 0, 0);
-        c[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[s] * q1[s], q1[s], c[2], 0, 0, 0);
+        c[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[s] * q1[s], q1[s], c[2], 0, 0, 0);
       }
     }
-  }
+  } while (HB < GRAM_WAVE_ROWS && (b0 += HB) < jb.e);
 #pragma unroll
   for (int u = 1; u < NA; u++)
 #pragma unroll
     for (int a = 0; a < NT; a++) acc[0][a] += acc[u][a];
   float *out = jb.nparts <= 1 ? G + (size_t)jb.col * KP * KP : gpart + (size_t)jb.slot * KP * KP;
-  // per-column cross Grams: the column tau w xsq_c QTQ, added once (by the
-  // column's first chunk; the slot sum carries it)
-  const float tw = (xsq && jb.flags == 0) ? w * xsq[jb.col] : 0.0f;
-  auto tau = [&](int m, int nn) { return xsq ? tw * QTQ[m * KP + nn] : 0.0f; };
+  const bool ct = Wt::column_tau && xsq;
+  const float tw = (ct && jb.flags == 0) ? w * xsq[jb.col] : 0.0f;
+  auto tau = [&](int m, int nn) { return ct ? tw * QTQ[m * KP + nn] : 0.0f; };
+  static_assert(Wt::column_tau || T == 1, "the plain-store epilogue writes one tile");
   // D register r of lane l: element m = 8(r/4) + 4(l/32) + r%4, n = l%32
 #pragma unroll
   for (int r = 0; r < 16; r++) {
     const int m = 8 * (r >> 2) + 4 * hf + (r & 3);
+    if constexpr (!Wt::column_tau) {  // plain stores: acc + 0 would not fold (and copies the accumulators to VGPRs)
+      out[m * KP + e] = acc[0][0][r];
+      continue;
+    }
     out[m * KP + e] = acc[0][0][r] + tau(m, e);
     if constexpr (T == 2) {
       out[m * KP + 32 + e] = acc[0][1][r] + tau(m, 32 + e);               // tile 01: rows 0..31, columns 32..63
@@ -1879,27 +1794,22 @@ __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma(uint64_t nchunks, const
   }
 }
 
-// The fp64 build at KP = 32 on the f64 matrix cores (v_mfma_f64_16x16x4f64,
-// MI355X guide: A lane l = A[m = l%16][k = l/16], B lane l = B[k = l/16][n =
-// l%16], D register r of lane l = element (row l/16 + 4r, column l%16)): four
-// positions are the K dimension, lane l holds w_r q_r[16t + l%16] / q_r[16t +
-// l%16] of position r = l/16 of the group; 32 positions per batch (one
-// coalesced index / weight load), tiles 00, 01 and 11 of the symmetric 32 x 32
-// Gram (10 stored as 01^T), two accumulator sets; the column tau added by the
-// column's first chunk as in k_hot_gram_mfma.
-static __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma_f64(uint64_t nchunks, const Job *__restrict__ chunks,
-                                                            const uint32_t *__restrict__ ycol,
-                                                            const double *__restrict__ wts,
-                                                            const double *__restrict__ Q1, uint64_t q1rows,
-                                                            double *__restrict__ G, double *__restrict__ gpart,
-                                                            const double *__restrict__ xsq,
-                                                            const double *__restrict__ QTQ, double w) {
+// fp64 at KP = 32 on the f64 matrix cores (v_mfma_f64_16x16x4f64, MI355X
+// guide: A lane l = A[m = l%16][k = l/16], B lane l = B[k = l/16][n = l%16],
+// D register r of lane l = element (row l/16 + 4r, column l%16)): four rows
+// are the K dimension, lane l holds w_r q_r[16t + l%16] / q_r[16t + l%16] of
+// row r = l/16 of the group; tiles 00, 01 and 11 of the symmetric 32 x 32
+// Gram (10 stored as 01^T).
+template <int KP, int HB, int NA, class Wt>
+__device__ __forceinline__ void gram_chunk_mfma(const Job jb, const uint32_t *__restrict__ idx, const Wt wt,
+                                                const double *__restrict__ Q1, uint64_t q1rows,
+                                                double *__restrict__ G, double *__restrict__ gpart,
+                                                const double *__restrict__ xsq, const double *__restrict__ QTQ,
+                                                double w) {
+  static_assert(KP == 32, "fp64 MFMA Gram builds: KP 32");
   typedef double d4 __attribute__((ext_vector_type(4)));
-  constexpr int KP = 32, HB = 32, NG = HB / 4, NA = 2;
+  constexpr int NG = HB / 4;
   const int lane = threadIdx.x & 63;
-  const uint64_t wv = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  if (wv >= nchunks) return;
-  const Job jb = chunks[wv];
   const BufView qb = buf_view(Q1, q1rows * KP * 8);
   const int c16 = lane & 15, rq = lane >> 4;
   d4 acc[NA][3];
@@ -1907,14 +1817,22 @@ static __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma_f64(uint64_t nch
   for (int u = 0; u < NA; u++)
 #pragma unroll
     for (int a = 0; a < 3; a++) acc[u][a] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int64_t b0 = jb.b; b0 < jb.e; b0 += HB) {
-    const int n = (int)(jb.e - b0 < HB ? jb.e - b0 : HB);
-    const uint32_t il = lane < n ? ycol[b0 + lane] : 0u;
-    const double wl = lane < n ? (wts ? wts[b0 + lane] : 1.0) : 0.0;
+  int64_t b0 = jb.b;
+  // HB = GRAM_WAVE_ROWS requires e - b <= HB (checked by the host, gram_launch):
+  // the chunk is one batch and the code has no loop, which keeps these
+  // instances at 8 (fp32) / 4 (fp64) waves per SIMD; with the loop 4 / 2.
+  do {  // (an empty chunk: one batch of zeros)
+    const int n = HB < GRAM_WAVE_ROWS ? (int)(jb.e - b0 < HB ? jb.e - b0 : HB) : (int)(jb.e - b0);
+    uint32_t il = 0u;
+    double wl = 0.0;
+    if (lane < n) {  // (one block: the index and weight loads issued together)
+      il = idx[b0 + lane];
+      wl = wt(b0 + lane, il);
+    }
     double q0[NG], q1[NG], wg[NG];
 #pragma unroll
     for (int g = 0; g < NG; g++) {
-      const int r = 4 * g + rq;  // positions past n read zero (buffer range check)
+      const int r = 4 * g + rq;  // rows past n read zero (buffer range check)
       const uint32_t i = (uint32_t)__shfl((int)il, r, 64);
       wg[g] = __shfl(wl, r, 64);
       const uint32_t off = r < n ? i * (uint32_t)(KP * 8) + (uint32_t)c16 * 8u : 0xffffffffu;
@@ -1929,21 +1847,70 @@ static __global__ __launch_bounds__(BLOCK) void k_hot_gram_mfma_f64(uint64_t nch
       c[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, q1[g], c[1], 0, 0, 0);
       c[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, q1[g], c[2], 0, 0, 0);
     }
-  }
+  } while (HB < GRAM_WAVE_ROWS && (b0 += HB) < jb.e);
 #pragma unroll
   for (int u = 1; u < NA; u++)
 #pragma unroll
     for (int a = 0; a < 3; a++) acc[0][a] += acc[u][a];
   double *out = jb.nparts <= 1 ? G + (size_t)jb.col * KP * KP : gpart + (size_t)jb.slot * KP * KP;
-  const double tw = (xsq && jb.flags == 0) ? w * xsq[jb.col] : 0.0;
-  auto tau = [&](int m, int nn) { return xsq ? tw * QTQ[m * KP + nn] : 0.0; };
+  const bool ct = Wt::column_tau && xsq;
+  const double tw = (ct && jb.flags == 0) ? w * xsq[jb.col] : 0.0;
+  auto tau = [&](int m, int nn) { return ct ? tw * QTQ[m * KP + nn] : 0.0; };
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int m = rq + 4 * r;
+    if constexpr (!Wt::column_tau) {  // plain stores, as above
+      out[m * KP + c16] = acc[0][0][r];
+      out[m * KP + 16 + c16] = acc[0][1][r];
+      out[(16 + c16) * KP + m] = acc[0][1][r];
+      out[(16 + m) * KP + 16 + c16] = acc[0][2][r];
+      continue;
+    }
     out[m * KP + c16] = acc[0][0][r] + tau(m, c16);
     out[m * KP + 16 + c16] = acc[0][1][r] + tau(m, 16 + c16);
     out[(16 + c16) * KP + m] = acc[0][1][r] + tau(16 + c16, m);
     out[(16 + m) * KP + 16 + c16] = acc[0][2][r] + tau(16 + m, 16 + c16);
+  }
+}
+
+template <typename real, int KP, int HB, int NA, class Wt>
+__global__ __launch_bounds__(BLOCK) void k_gram_build_mfma(uint64_t nchunks, const Job *__restrict__ chunks,
+                                                           const uint32_t *__restrict__ idx, const Wt wt,
+                                                           const real *__restrict__ Q1, uint64_t q1rows,
+                                                           real *__restrict__ G, real *__restrict__ gpart,
+                                                           const real *__restrict__ xsq, const real *__restrict__ QTQ,
+                                                           real w) {
+  const uint64_t wv = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  if (wv >= nchunks) return;
+  gram_chunk_mfma<KP, HB, NA>(chunks[wv], idx, wt, Q1, q1rows, G, gpart, xsq, QTQ, w);
+}
+
+// G of a multi-chunk Gram = its partial slots summed in slot order (sums:
+// Job{col = the Gram, nparts, slot = first partial slot}); blockIdx.x: the
+// Gram, blockIdx.y: a range of BLOCK vectors of SLOT_VE of its elements; the
+// slots are read GB at a time (loads in flight).  fp32 at KP = 32 (the side
+// column and pair Grams' default): 16-byte vectors, one block per Gram (one
+// element per thread measured + 0.6 us per kkbox pair-Gram build); else one
+// element per thread, which keeps a column of a few hundred chunks in flight.
+template <typename real, int KP> constexpr int slot_sum_ve() { return sizeof(real) == 4 && KP == 32 ? 4 : 1; }
+template <typename real, int KP>
+__global__ __launch_bounds__(BLOCK) void k_gram_slot_sum(const Job *__restrict__ sums, const real *__restrict__ gpart,
+                                                         real *__restrict__ G) {
+  constexpr int KK = KP * KP, VE = slot_sum_ve<real, KP>(), NV = KK / VE, GB = 8;
+  typedef real vt __attribute__((ext_vector_type(VE)));
+  const Job jb = sums[blockIdx.x];
+  for (int t = blockIdx.y * BLOCK + threadIdx.x; t < NV; t += gridDim.y * BLOCK) {
+    const vt *src = reinterpret_cast<const vt *>(gpart + (size_t)jb.slot * KK) + t;
+    vt acc = src[0];
+    for (uint32_t q0 = 1; q0 < jb.nparts; q0 += GB) {
+      vt y[GB];
+#pragma unroll
+      for (int u = 0; u < GB; u++) y[u] = q0 + u < jb.nparts ? src[(size_t)(q0 + u) * NV] : (vt)(real)0;
+#pragma unroll
+      for (int u = 0; u < GB; u++)
+        if (q0 + u < jb.nparts) acc += y[u];
+    }
+    reinterpret_cast<vt *>(G + (size_t)jb.col * KK)[t] = acc;
   }
 }
 
@@ -1977,30 +1944,6 @@ __global__ __launch_bounds__(BLOCK) void k_ccg_gather(uint64_t P, const uint32_t
   const double x = (double)xval[rid[p]];
   cpos[t] = ycol[p];
   cw[t] = (real)((1 - w) * x * x);
-}
-
-// G of a multi-chunk row = its partial slots summed in slot order (sums:
-// Job{col = Gram slot, nparts, slot = first partial slot}); blockIdx.x: the
-// Gram, blockIdx.y: a range of BLOCK of its elements (a column of a few
-// hundred chunks keeps one element per thread in flight).
-template <typename real, int KP>
-__global__ __launch_bounds__(BLOCK) void k_hot_slot_sum(const Job *__restrict__ sums, const real *__restrict__ gpart,
-                                                        real *__restrict__ G) {
-  constexpr int KK = KP * KP, GB = 8;
-  const Job jb = sums[blockIdx.x];
-  for (int t = blockIdx.y * BLOCK + threadIdx.x; t < KK; t += gridDim.y * BLOCK) {
-    const real *src = gpart + (size_t)jb.slot * KK + t;
-    real acc = src[0];
-    for (uint32_t q0 = 1; q0 < jb.nparts; q0 += GB) {
-      real y[GB];
-#pragma unroll
-      for (int u = 0; u < GB; u++) y[u] = q0 + u < jb.nparts ? src[(size_t)(q0 + u) * KK] : (real)0;
-#pragma unroll
-      for (int u = 0; u < GB; u++)
-        if (q0 + u < jb.nparts) acc += y[u];
-    }
-    G[(size_t)jb.col * KK + t] = acc;
-  }
 }
 
 // One CG step of a Gram side half: per column, the direction p_c of
@@ -2042,7 +1985,7 @@ __global__ __launch_bounds__(BLOCK) void k_hv_cgram(uint64_t D, const real *__re
 // The field block of the side Hessian (hs_side, ffm.cpp:594-628) is
 //   (H v)_a = sum_b G_ab v_b,  G_ab = sum_{i: X_ia X_ib != 0} d_i X_ia X_ib q_i q_i^T,
 // one k x k Gram per feature pair (a <= b) present in some row, built once
-// per half (k_col_gram* with pair weights).  A CG step is then ONE launch
+// per half (k_gram_build_mfma / k_col_gram with pair weights).  A CG step is then ONE launch
 // instead of the row pass over every row plus a feature pass whose heavy
 // columns (~500 rows each) cost a chain of dependent rounds (~21 us per
 // step): block a sums G_ab p_b over feature a's pairs (its subgroups split
@@ -2564,7 +2507,7 @@ __global__ __launch_bounds__(BLOCK, sizeof(real) * SMAX <= 16 ? 4 : 2) void k_cg
 // are k_hs_cross_seg's over the row's positives; the tau term takes QTQ
 // from LDS (k_feat TAU's per-column form); a hot row (hot_row[i] !=
 // HOT_NONE: more positives than one gather pass) reads its Gram
-// G_i = sum_j q_j q_j^T (k_hot_gram, built for the half), so no subgroup
+// G_i = sum_j q_j q_j^T (k_gram_build*, built for the half), so no subgroup
 // walks a popular item's thousands of positives.
 template <typename real, int KP> constexpr bool xfuse_kp() { return KP <= 64; }  // (QTQ in LDS)
 // XGB: gathers per round (8: 4 waves per SIMD at <= 128 registers; 16:

@@ -136,7 +136,7 @@ template <typename real> struct DevField {
   // Allocated on the first Gram half (col_grams); gpart holds the ordered
   // partial slots of multi-chunk columns (gslots of them).
   DevBuf<Job> gchunks;
-  DevBuf<Job> gsums;  // MFMA build (k_col_gram32): multi-chunk columns {col, nparts, first slot}
+  DevBuf<Job> gsums;  // multi-chunk columns {col, nparts, first slot}
   DevBuf<real> gram, gpart;
   uint64_t gslots = 0;
   // Owned field (several ranks): every feature is touched by the
@@ -199,7 +199,7 @@ template <typename real> struct DevSide {
   DevBuf<uint32_t> sord;  // the cross row passes' processing order of the segments (longest first)
   bool short_segs = false;  // >= 99 % of the segments hold <= 16 positives (k_hs_cross_seg's 16-position pass)
   DevBuf<uint32_t> segptr;
-  // Hot rows (kernels.hpp k_hot_gram*): rows with >= hot_min positives whose
+  // Hot rows (kernels.hpp k_gram_build*): rows with >= hot_min positives whose
   // cross-half Hessian-vector rows read a k x k Gram of their partner rows
   // (built once per cross half) instead of gathering them every CG step.
   uint64_t nhot = 0, hslots = 0, hpos = 0;  // rows, partial slots, their positives
@@ -2736,14 +2736,17 @@ template <typename real> class Problem final : public ProblemBase {
   // Gram build chunks of a list of position ranges (one Gram per range):
   // ~HOT_CHUNK_MAX positions per chunk, at most 64 chunks per Gram; the
   // chunks of a multi-chunk Gram write consecutive partial slots, summed in
-  // slot order by k_hot_slot_sum (sums: {gram, nparts, first slot}).
-  static void gram_chunks(const std::vector<std::pair<uint64_t, uint64_t>> &ranges, std::vector<Job> &chunks,
-                          std::vector<Job> &sums, uint64_t &slots, uint64_t cmax = HOT_CHUNK_MAX,
-                          uint64_t npmax = 64) {
+  // slot order by k_gram_slot_sum (sums: {gram, nparts, first slot}).  An
+  // empty range gets one empty chunk, so that its Gram is stored as zero.
+  // npmax = 0: chunks of exactly cmax (the last one shorter), any number.
+  using Ranges = std::vector<std::pair<uint64_t, uint64_t>>;
+  static void gram_chunks(const Ranges &ranges, std::vector<Job> &chunks, std::vector<Job> &sums, uint64_t &slots,
+                          uint64_t cmax = HOT_CHUNK_MAX, uint64_t npmax = 64) {
     for (uint64_t g = 0; g < ranges.size(); g++) {
       const uint64_t b = ranges[g].first, e = ranges[g].second;
-      const uint64_t np = std::max<uint64_t>(1, std::min<uint64_t>(npmax, (e - b + cmax - 1) / cmax));
-      const uint64_t len = (e - b + np - 1) / std::max<uint64_t>(np, 1);
+      const uint64_t want = (e - b + cmax - 1) / cmax;
+      const uint64_t np = std::max<uint64_t>(1, npmax ? std::min(npmax, want) : want);
+      const uint64_t len = npmax ? (e - b + np - 1) / np : cmax;
       for (uint64_t q = 0; q < np; q++)
         chunks.push_back(Job{(uint32_t)g, (uint32_t)np, np > 1 ? (uint32_t)(slots + q) : 0u, (uint32_t)q,
                              (int64_t)std::min(e, b + q * len), (int64_t)std::min(e, b + (q + 1) * len)});
@@ -2799,74 +2802,127 @@ template <typename real> class Problem final : public ProblemBase {
     return hot_env_ && hot_now_ && h.cross && h.own->nhot > 0 && hotG_.p && !ccg_now_;
   }
 
+  // One Gram build from gathered rows (kernels.hpp k_gram_build*): per
+  // chunk job, sum_p wt(p) q_idx[p] q_idx[p]^T over rows of Q1 into G, or
+  // into the partial slots of part, which are then summed in slot order.
+  // Callers set the fields by name; what a build does not use stays null.
+  struct GramBuild {
+    const char *name = nullptr;  // profiling family, its algorithmic bytes and flops
+    double bytes = 0, flops = 0;
+    const DevBuf<Job> *chunks = nullptr, *sums = nullptr;
+    const uint32_t *idx = nullptr;  // the entries' rows of Q1 (q1rows rows)
+    const real *Q1 = nullptr;
+    uint64_t q1rows = 0;
+    real *G = nullptr, *part = nullptr;  // ngram Grams, the partial slots
+    uint64_t ngram = 0;
+    // list weights (hess = false): wts[p], or 1 without wts; optionally
+    // + w xsq[col] qtq on every Gram
+    const real *wts = nullptr, *xsq = nullptr, *qtq = nullptr;
+    // Hessian weights (hess = true): ((1 - w) (cnt[i + 1] - cnt[i]) + w n1) val[p]^2
+    // (pw: val[p]) of the entry's row i; tick: per-Gram arrival tickets of
+    // the VALU build (zero at rest)
+    bool hess = false;
+    const real *val = nullptr;
+    const int64_t *cnt = nullptr;
+    double n1 = 0;
+    int pw = 0;
+    unsigned *tick = nullptr;
+  };
+  template <int KP, int HB, int NA, class Wt> void gram_launch(const GramBuild &b, Wt wt) {
+    constexpr bool f32 = std::is_same<real, float>::value, hess = std::is_same<Wt, WtHess<real>>::value;
+    // on the matrix cores at KP = 32, and in fp32 at KP = 64 for list weights
+    // (the Hessian weights' chunks are cut for a wave only at KP = 32)
+    constexpr bool has_mfma = KP == 32 || (KP == 64 && f32 && !hess);
+    bool mfma = false;
+    if constexpr (has_mfma) {
+      if (!no_mfma_) {
+        // HB = GRAM_WAVE_ROWS: the kernel takes a chunk as ONE batch, so the
+        // chunks must have been cut to at most HB rows (gram_chunks with
+        // side_chunk_rows, the cut of every Hessian-weight build)
+        if (HB == GRAM_WAVE_ROWS && (!hess || side_chunk_rows() > (uint64_t)HB))
+          throw Error(OCFFM_E_STATE, "Gram build: chunks longer than one wave batch");
+        launch(k_gram_build_mfma<real, KP, HB, NA, Wt>, (unsigned)((b.chunks->n + 3) / 4), BLOCK, 0,
+               (uint64_t)b.chunks->n, (const Job *)b.chunks->p, b.idx, wt, b.Q1, b.q1rows, b.G, b.part, b.xsq, b.qtq,
+               (real)w_);  // tau folded in
+        mfma = true;
+      }
+    }
+    // the VALU build of the Hessian-weight Grams sums its multi-chunk columns
+    // itself (k_col_gram's tickets: the slot-sum launch cost it + 4 us at kdd12)
+    if (!mfma) {
+      if constexpr (hess)
+        launch(k_col_gram<real, KP>, (unsigned)b.chunks->n, BLOCK, 0, (const Job *)b.chunks->p, b.idx, b.val, b.cnt,
+               b.Q1, w_, b.n1, b.G, b.part, b.tick, b.pw);
+      else
+        launch(k_gram_build<real, KP>, (unsigned)b.chunks->n, BLOCK, 0, (const Job *)b.chunks->p, b.idx, b.wts, b.Q1,
+               b.G, b.part);
+    }
+    if (b.sums->n && (mfma || !hess)) {
+      constexpr unsigned nv = KP * KP / slot_sum_ve<real, KP>();
+      launch(k_gram_slot_sum<real, KP>, dim3((unsigned)b.sums->n, (nv + BLOCK - 1) / BLOCK), BLOCK, 0,
+             (const Job *)b.sums->p, (const real *)b.part, b.G);
+    }
+    if (!mfma && b.xsq)
+      launch(k_gram_add_tau<real, KP>, grid_for(b.ngram * KP * KP, BLOCK, 2048), BLOCK, 0, b.ngram, b.G, b.xsq, b.qtq,
+             w_);
+  }
+  void build_grams(const GramBuild &b) {
+    with_kp(kp_, [&](auto K) {
+      constexpr int KP = decltype(K)::value;
+      prof_launch(b.name, b.bytes, [&] {
+        if (b.hess)
+          gram_launch<KP, GRAM_WAVE_ROWS, std::is_same<real, float>::value ? 1 : 2>(
+              b, WtHess<real>{b.val, b.cnt, w_, b.n1, b.pw});
+        else
+          gram_launch<KP, 32, 2>(b, WtList<real>{b.wts});
+      }, b.flops);
+    });
+  }
+
   // The hot rows' Grams G_i = sum_{j in Omega_i} q_j q_j^T over this half's
   // partner table (fixed over the half's CG steps).
   void hot_grams(const HalfCtx &h, bool force = false) {
     if (!(force ? h.own->nhot > 0 && hotG_.p : hot(h))) return;
     DevSide<real> &own = *h.own;
-    with_kp(kp_, [&](auto K) {
-      constexpr int KP = decltype(K)::value;
-      const double rs = sizeof(real);
-      const double bytes = (double)own.hpos * (4 + KP * rs) + (double)own.nhot * KP * KP * rs +
-                           (double)own.hslots * KP * KP * rs * 2;
-      prof_launch("hot_gram", bytes, [&] {
-        bool done = false;
-        if constexpr (std::is_same<real, float>::value && (KP == 32 || KP == 64)) {
-          if (!no_mfma_) {
-            launch(k_hot_gram_mfma<KP>, (unsigned)((own.hchunks.n + 3) / 4), BLOCK, 0, (uint64_t)own.hchunks.n,
-                   (const Job *)own.hchunks.p, (const uint32_t *)own.ycol.p, (const float *)nullptr, (const float *)h.Q1,
-                   (uint64_t)h.partner->R, (float *)hotG_.p, (float *)hotP_.p, (const float *)nullptr,
-                   (const float *)nullptr, 0.0f);
-            done = true;
-          }
-        }
-        if constexpr (std::is_same<real, double>::value && KP == 32) {
-          if (!no_mfma_) {
-            launch(k_hot_gram_mfma_f64, (unsigned)((own.hchunks.n + 3) / 4), BLOCK, 0, (uint64_t)own.hchunks.n,
-                   (const Job *)own.hchunks.p, (const uint32_t *)own.ycol.p, (const double *)nullptr,
-                   (const double *)h.Q1, (uint64_t)h.partner->R, (double *)hotG_.p, (double *)hotP_.p,
-                   (const double *)nullptr, (const double *)nullptr, 0.0);
-            done = true;
-          }
-        }
-        if (!done)
-          launch(k_hot_gram<real, KP>, (unsigned)own.hchunks.n, BLOCK, 0, (const Job *)own.hchunks.p,
-                 (const uint32_t *)own.ycol.p, (const real *)nullptr, (const real *)h.Q1, hotG_.p, hotP_.p);
-        if (own.hsums.n)
-          launch(k_hot_slot_sum<real, KP>, dim3((unsigned)own.hsums.n, (KP * KP + BLOCK - 1) / BLOCK), BLOCK, 0,
-                 (const Job *)own.hsums.p, (const real *)hotP_.p, hotG_.p);
-      }, 2.0 * own.hpos * KP * KP);
-    });
+    const double kk = (double)kp_ * kp_, rs = sizeof(real);
+    GramBuild b;
+    b.name = "hot_gram";
+    b.bytes = (double)own.hpos * (4 + kp_ * rs) + (double)own.nhot * kk * rs + (double)own.hslots * kk * rs * 2;
+    b.flops = 2.0 * own.hpos * kk;
+    b.chunks = &own.hchunks, b.sums = &own.hsums, b.idx = own.ycol.p;
+    b.Q1 = h.Q1, b.q1rows = h.partner->R;
+    b.G = hotG_.p, b.part = hotP_.p, b.ngram = own.nhot;
+    build_grams(b);
   }
 
   // Gram chunks of a one-node-per-row field (build_csc's column order): each
-  // column in chunks of at most cgram_rows rows (one LDS stage: larger
-  // OCFFM_CGRAM_CHUNK values are capped there); empty columns get one empty
-  // chunk so that their G_c is stored as zero.  The chunks of a multi-chunk
-  // column get consecutive partial slots (Job.slot) and their index in the
-  // column (Job.flags).  The Gram buffers are allocated by col_grams.
+  // column in chunks of at most side_chunk_rows rows; empty columns get one
+  // empty chunk so that their G_c is stored as zero.  The chunks of a
+  // multi-chunk column get consecutive partial slots (Job.slot) and their
+  // index in the column (Job.flags).  The Gram buffers are allocated by
+  // col_grams.
   void col_gram_chunks(DevField<real> &F, const std::vector<int64_t> &cptr) {
-    const uint64_t ch = cgram32() ? (uint64_t)CGRAM32_ROWS
-                                  : std::min<uint64_t>(cgram_chunk_, (uint64_t)cgram_rows((int)kp_, (int)sizeof(real)));
     std::vector<Job> chunks, sums;
-    uint64_t slots = 0;
-    for (uint64_t d = 0; d < F.D; d++) {
-      const uint64_t b = cptr[d], e = cptr[d + 1];
-      const uint32_t np = (uint32_t)std::max<uint64_t>(1, (e - b + ch - 1) / ch);
-      for (uint32_t q = 0; q < np; q++)
-        chunks.push_back(Job{(uint32_t)d, np, np > 1 ? (uint32_t)(slots + q) : 0u, q,
-                             (int64_t)std::min(e, b + q * ch), (int64_t)std::min(e, b + (q + 1) * ch)});
-      if (np > 1) sums.push_back(Job{(uint32_t)d, np, (uint32_t)slots, 0u, 0, 0});
-      if (np > 1) slots += np;
-    }
-    if (slots > 0xffffffffull) throw Error(OCFFM_E_DATA, "too many Gram chunks in one field");
+    F.gslots = 0;
+    gram_chunks(ptr_ranges(cptr, F.D), chunks, sums, F.gslots, side_chunk_rows(), 0);
     F.gchunks.upload(chunks);
-    if (cgram32() && !sums.empty()) F.gsums.upload(sums);
-    F.gslots = slots;
+    F.gsums.upload(sums);
+  }
+  static Ranges ptr_ranges(const std::vector<int64_t> &ptr, uint64_t n) {
+    Ranges r(n);
+    for (uint64_t d = 0; d < n; d++) r[d] = {(uint64_t)ptr[d], (uint64_t)ptr[d + 1]};
+    return r;
+  }
+  // Rows per chunk of the side column and pair Grams: one wave's batch on
+  // the matrix cores, else at most one LDS stage (larger OCFFM_CGRAM_CHUNK
+  // values are capped there).
+  uint64_t side_chunk_rows() const {
+    return cgram32() ? (uint64_t)GRAM_WAVE_ROWS
+                     : std::min<uint64_t>(cgram_chunk_, (uint64_t)cgram_rows((int)kp_, (int)sizeof(real)));
   }
 
-  // KP = 32: the Grams are built on the matrix cores (kernels.hpp
-  // k_col_gram32, fp32; k_col_gram_f64, fp64)
+  // KP = 32: the side column and pair Grams are built on the matrix cores
+  // (kernels.hpp k_gram_build_mfma)
   bool cgram32() const { return kp_ == 32 && !no_mfma_; }
 
   // Side half whose CG steps run on per-column Grams (several ranks: each
@@ -2994,14 +3050,12 @@ template <typename real> class Problem final : public ProblemBase {
     std::vector<int64_t> cp(F.D + 1);
     HIPCHK(hipMemcpyAsync(cp.data(), cptr.p, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
     sync();
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(F.D);
-    for (uint64_t c = 0; c < F.D; c++) ranges[c] = {(uint64_t)cp[c], (uint64_t)cp[c + 1]};
     std::vector<Job> chunks, sums;
     uint64_t slots = 0;
     // one chunk per column where the columns alone fill the chip (artist:
     // 5,000 columns of ~420 positions: no partial slots to sum); a Pareto
     // head column (millions of positions) in up to 256 chunks
-    gram_chunks(ranges, chunks, sums, slots, F.D >= 2048 ? 1024 : HOT_CHUNK_MAX, 256);
+    gram_chunks(ptr_ranges(cp, F.D), chunks, sums, slots, F.D >= 2048 ? 1024 : HOT_CHUNK_MAX, 256);
     F.cchunks.upload(chunks);
     F.csums.upload(sums);
     F.cslots = slots;
@@ -3010,45 +3064,20 @@ template <typename real> class Problem final : public ProblemBase {
     if (slots * kp_ * kp_ > ccgP_.n) ccgP_.alloc(slots * kp_ * kp_, false);
     F.ccg_ready = true;
   }
-  // C_c of every column for this half (needs qtq_: gradient() sets it)
+  // C_c of every column for this half (needs qtq_: gradient() sets it); the
+  // column tau is folded in by the MFMA build, else added by k_gram_add_tau
   void ccg_build(const HalfCtx &h) {
     DevField<real> &F = *h.F;
-    with_kp(kp_, [&](auto K) {
-      constexpr int KP = decltype(K)::value;
-      const double rs = sizeof(real);
-      const double bytes = (double)F.cnpos * (8 + KP * rs) + (double)F.D * KP * KP * rs * 3 +
-                           (double)F.cslots * KP * KP * rs * 2;
-      prof_launch("ccg_build", bytes, [&] {
-        bool done = false;
-        if constexpr (std::is_same<real, float>::value && (KP == 32 || KP == 64)) {
-          if (!no_mfma_) {
-            launch(k_hot_gram_mfma<KP>, (unsigned)((F.cchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.cchunks.n,
-                   (const Job *)F.cchunks.p, (const uint32_t *)F.cpos.p, (const float *)F.cw.p,
-                   (const float *)h.Q1, (uint64_t)h.partner->R, (float *)ccgG_.p, (float *)ccgP_.p,
-                   (const float *)F.xsq.p, (const float *)qtq_, (float)w_);  // tau folded in
-            done = true;
-          }
-        }
-        if constexpr (std::is_same<real, double>::value && KP == 32) {
-          if (!no_mfma_) {
-            launch(k_hot_gram_mfma_f64, (unsigned)((F.cchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.cchunks.n,
-                   (const Job *)F.cchunks.p, (const uint32_t *)F.cpos.p, (const double *)F.cw.p,
-                   (const double *)h.Q1, (uint64_t)h.partner->R, (double *)ccgG_.p, (double *)ccgP_.p,
-                   (const double *)F.xsq.p, (const double *)qtq_, w_);  // tau folded in
-            done = true;
-          }
-        }
-        if (!done)
-          launch(k_hot_gram<real, KP>, (unsigned)F.cchunks.n, BLOCK, 0, (const Job *)F.cchunks.p,
-                 (const uint32_t *)F.cpos.p, (const real *)F.cw.p, (const real *)h.Q1, ccgG_.p, ccgP_.p);
-        if (F.csums.n)
-          launch(k_hot_slot_sum<real, KP>, dim3((unsigned)F.csums.n, (KP * KP + BLOCK - 1) / BLOCK), BLOCK, 0,
-                 (const Job *)F.csums.p, (const real *)ccgP_.p, ccgG_.p);
-        if (!done)
-          launch(k_gram_add_tau<real, KP>, grid_for(F.D * KP * KP, BLOCK, 2048), BLOCK, 0, (uint64_t)F.D, ccgG_.p,
-                 (const real *)F.xsq.p, (const real *)qtq_, w_);
-      }, 2.0 * F.cnpos * KP * KP);
-    });
+    const double kk = (double)kp_ * kp_, rs = sizeof(real);
+    GramBuild b;
+    b.name = "ccg_build";
+    b.bytes = (double)F.cnpos * (8 + kp_ * rs) + (double)F.D * kk * rs * 3 + (double)F.cslots * kk * rs * 2;
+    b.flops = 2.0 * F.cnpos * kk;
+    b.chunks = &F.cchunks, b.sums = &F.csums, b.idx = F.cpos.p;
+    b.Q1 = h.Q1, b.q1rows = h.partner->R;
+    b.G = ccgG_.p, b.part = ccgP_.p, b.ngram = F.D;
+    b.wts = F.cw.p, b.xsq = F.xsq.p, b.qtq = qtq_;
+    build_grams(b);
   }
 
   // Does a side half over a one-node-per-row field (R rows, D columns) pay
@@ -3136,22 +3165,11 @@ template <typename real> class Problem final : public ProblemBase {
     F.pgrow.upload(prow);
     F.pgval.upload(to_real(pw));
     // Gram build chunks (col_gram_chunks' cut, over the pairs' entries)
-    const uint64_t ch = cgram32() ? (uint64_t)CGRAM32_ROWS
-                                  : std::min<uint64_t>(cgram_chunk_, (uint64_t)cgram_rows((int)kp_, (int)sizeof(real)));
     std::vector<Job> chunks, sums;
-    uint64_t slots = 0;
-    for (uint64_t d = 0; d < np; d++) {
-      const uint64_t b = pptr[d], e = pptr[d + 1];
-      const uint32_t n = (uint32_t)std::max<uint64_t>(1, (e - b + ch - 1) / ch);
-      for (uint32_t q = 0; q < n; q++)
-        chunks.push_back(Job{(uint32_t)d, n, n > 1 ? (uint32_t)(slots + q) : 0u, q, (int64_t)std::min(e, b + q * ch),
-                             (int64_t)std::min(e, b + (q + 1) * ch)});
-      if (n > 1) sums.push_back(Job{(uint32_t)d, n, (uint32_t)slots, 0u, 0, 0});
-      if (n > 1) slots += n;
-    }
+    F.pgslots = 0;
+    gram_chunks(ptr_ranges(pptr, np), chunks, sums, F.pgslots, side_chunk_rows(), 0);
     F.pgchunks.upload(chunks);
-    if (cgram32() && !sums.empty()) F.pgsums.upload(sums);
-    F.pgslots = slots;
+    F.pgsums.upload(sums);
     F.pgcnt.alloc(np);
     // adjacency: feature a <- (p, b) for p = (a, b), and b <- (p, a) for a != b
     std::vector<int64_t> ap(F.D + 1, 0);
@@ -3181,43 +3199,20 @@ template <typename real> class Problem final : public ProblemBase {
     if (F.D * F.pqb * kp_ > pgt_.n) pgt_.alloc(F.D * F.pqb * kp_);
     F.pg = true;
   }
-  // The half's pair Grams (k_col_gram* with pair weights: d_i X_ia X_ib).
+  // The half's pair Grams (Hessian weights with pair values: d_i X_ia X_ib).
   void pair_grams(const HalfCtx &h) {
     DevField<real> &F = *h.F;
     if (!F.pgram.p) F.pgram.alloc(F.npair * kp_ * kp_, false);
     if (F.pgslots && !F.pgpart.p) F.pgpart.alloc(F.pgslots * kp_ * kp_, false);
-    with_kp(kp_, [&](auto K) {
-      constexpr int KP = decltype(K)::value;
-      const double rs = sizeof(real);
-      prof_launch("pair_gram", (double)F.pgrow.n * (8 + rs + 16 + KP * rs) + (double)F.pgram.bytes(), [&] {
-        if constexpr (std::is_same<real, float>::value && KP == 32) {
-          if (cgram32()) {
-            launch(k_col_gram32, (unsigned)((F.pgchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.pgchunks.n,
-                   (const Job *)F.pgchunks.p, (const uint32_t *)F.pgrow.p, (const float *)F.pgval.p, hess_cnt(h),
-                   (const float *)h.Q1, (uint64_t)h.own->R, w_, hess_n1(h), (float *)F.pgram.p, (float *)F.pgpart.p,
-                   1);
-            if (F.pgsums.n)
-              launch(k_gram_slot_sum, (unsigned)F.pgsums.n, BLOCK, 0, (const Job *)F.pgsums.p,
-                     (const float *)F.pgpart.p, (float *)F.pgram.p);
-            return;
-          }
-        }
-        if constexpr (std::is_same<real, double>::value && KP == 32) {
-          if (cgram32()) {
-            launch(k_col_gram_f64, (unsigned)((F.pgchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.pgchunks.n,
-                   (const Job *)F.pgchunks.p, (const uint32_t *)F.pgrow.p, (const double *)F.pgval.p, hess_cnt(h),
-                   (const double *)h.Q1, (uint64_t)h.own->R, w_, hess_n1(h), (double *)F.pgram.p,
-                   (double *)F.pgpart.p, 1);
-            if (F.pgsums.n)
-              launch(k_hot_slot_sum<double, 32>, dim3((unsigned)F.pgsums.n, (1024 + BLOCK - 1) / BLOCK), BLOCK, 0,
-                     (const Job *)F.pgsums.p, (const double *)F.pgpart.p, (double *)F.pgram.p);
-            return;
-          }
-        }
-        launch(k_col_gram<real, KP>, (unsigned)F.pgchunks.n, BLOCK, 0, F.pgchunks.p, F.pgrow.p, F.pgval.p,
-               hess_cnt(h), h.Q1, w_, hess_n1(h), F.pgram.p, F.pgpart.p, F.pgcnt.p, 1);
-      });
-    });
+    const double rs = sizeof(real);
+    GramBuild b;
+    b.name = "pair_gram";
+    b.bytes = (double)F.pgrow.n * (8 + rs + 16 + kp_ * rs) + (double)F.pgram.bytes();
+    b.chunks = &F.pgchunks, b.sums = &F.pgsums, b.idx = F.pgrow.p;
+    b.Q1 = h.Q1, b.q1rows = h.own->R;
+    b.G = F.pgram.p, b.part = F.pgpart.p, b.ngram = F.npair;
+    b.hess = true, b.val = F.pgval.p, b.cnt = hess_cnt(h), b.n1 = hess_n1(h), b.pw = 1, b.tick = F.pgcnt.p;
+    build_grams(b);
   }
   // One CG step of a pair-Gram half: one launch (k_pg_step), or with many
   // features the pair products into acc and the unfused finalisation.
@@ -3256,41 +3251,17 @@ template <typename real> class Problem final : public ProblemBase {
       return;
     }
     DevField<real> &F = *h.F;
-    DevSide<real> &other = h.user ? V_ : U_;
-    if (!F.gram.p) F.gram.alloc(F.D * kp_ * kp_, false);  // every column is stored by its last chunk
+    if (!F.gram.p) F.gram.alloc(F.D * kp_ * kp_, false);  // every column is stored (empty ones as zero)
     if (F.gslots && !F.gpart.p) F.gpart.alloc(F.gslots * kp_ * kp_, false);
-    with_kp(kp_, [&](auto K) {
-      constexpr int KP = decltype(K)::value;
-      const double rs = sizeof(real);
-      prof_launch("col_gram", (double)F.nnz * (8 + rs + 16 + KP * rs) + (double)F.gram.bytes(), [&] {
-        if constexpr (std::is_same<real, float>::value && KP == 32) {
-          if (cgram32()) {
-            // (q1: the same-side partner table, one row per row of this side)
-            launch(k_col_gram32, (unsigned)((F.gchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.gchunks.n,
-                   (const Job *)F.gchunks.p, (const uint32_t *)F.crow.p, (const float *)F.cval.p, hess_cnt(h),
-                   (const float *)h.Q1, (uint64_t)h.own->R, w_, hess_n1(h), (float *)F.gram.p, (float *)F.gpart.p, 0);
-            if (F.gsums.n)
-              launch(k_gram_slot_sum, (unsigned)F.gsums.n, BLOCK, 0, (const Job *)F.gsums.p,
-                     (const float *)F.gpart.p, (float *)F.gram.p);
-            return;
-          }
-        }
-        if constexpr (std::is_same<real, double>::value && KP == 32) {
-          if (cgram32()) {
-            launch(k_col_gram_f64, (unsigned)((F.gchunks.n + 3) / 4), BLOCK, 0, (uint64_t)F.gchunks.n,
-                   (const Job *)F.gchunks.p, (const uint32_t *)F.crow.p, (const double *)F.cval.p, hess_cnt(h),
-                   (const double *)h.Q1, (uint64_t)h.own->R, w_, hess_n1(h), (double *)F.gram.p,
-                   (double *)F.gpart.p, 0);
-            if (F.gsums.n)
-              launch(k_hot_slot_sum<double, 32>, dim3((unsigned)F.gsums.n, (1024 + BLOCK - 1) / BLOCK), BLOCK, 0,
-                     (const Job *)F.gsums.p, (const double *)F.gpart.p, (double *)F.gram.p);
-            return;
-          }
-        }
-        launch(k_col_gram<real, KP>, (unsigned)F.gchunks.n, BLOCK, 0, F.gchunks.p, F.crow.p, F.cval.p,
-               hess_cnt(h), h.Q1, w_, hess_n1(h), F.gram.p, F.gpart.p, F.cnt.p, 0);
-      });
-    });
+    const double rs = sizeof(real);
+    GramBuild b;
+    b.name = "col_gram";
+    b.bytes = (double)F.nnz * (8 + rs + 16 + kp_ * rs) + (double)F.gram.bytes();
+    b.chunks = &F.gchunks, b.sums = &F.gsums, b.idx = F.crow.p;
+    b.Q1 = h.Q1, b.q1rows = h.own->R;  // (the same-side partner table, one row per row of this side)
+    b.G = F.gram.p, b.part = F.gpart.p, b.ngram = F.D;
+    b.hess = true, b.val = F.cval.p, b.cnt = hess_cnt(h), b.n1 = hess_n1(h), b.pw = 0, b.tick = F.cnt.p;
+    build_grams(b);
   }
 
   // Column tau: the w phi_i QTQ term of a cross half's Hessian-vector rows,

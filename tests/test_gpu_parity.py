@@ -108,7 +108,7 @@ def test_init_state(tiny):
 def test_gradient_and_hv_kernels(self_side, hot, monkeypatch):
     """Every half's gradient and Hessian-vector product (fp64) against the
     oracle.  OCFFM_HOT=2: every cross-half row with >= 2 positives reads a
-    per-row Gram of its partner rows (k_hot_gram) instead of gathering them."""
+    per-row Gram of its partner rows (k_gram_build) instead of gathering them."""
     if hot:
         monkeypatch.setenv("OCFFM_HOT", hot)
     ds = synth.general(seed=5, m=60, n=40, fu=2, fv=2, k=5, nnz_user=2, mean_pos=3.0, vals="real")
@@ -147,53 +147,120 @@ def test_gradient_order_independent():
 KK_RC = dict(seed=3, m=1500, n=4000, mean=20.0, name="kk_rc")  # ~24 % heavy positives on both sides
 
 
-@pytest.mark.parametrize("env", [{}, {"OCFFM_NO_MFMA": "1"}, {"OCFFM_CGRAM": "2"},
-                                 {"OCFFM_CGRAM": "2", "OCFFM_NO_MFMA": "1"}, {"OCFFM_TPRE": "1"},
-                                 {"OCFFM_HOT": "0"}, {"OCFFM_HOT": "2"}, {"OCFFM_HOT": "2", "OCFFM_NO_MFMA": "1"},
-                                 {"OCFFM_CCG": "2"}, {"OCFFM_CCG": "2", "OCFFM_NO_MFMA": "1"}])
+GRAM_EDGE_COLS = (1, 31, 32, 0, 33, 63, 64, 65, 129)  # rows of the user field's columns
+GRAM_EDGE_POS = (1, 2, 31, 32, 33, 64, 65, 257)  # the user rows' positive counts, cycled
+
+
+def gram_edges():
+    """A hand-built set (k = 32, real-valued x) on the chunk boundaries of the
+    Gram builds from gathered rows (kernels.hpp k_gram_build*).  418 users
+    with ONE one-node field of 9 columns of 1, 31, 32, 0, 33, 63, 64, 65 and
+    129 rows (OCFFM_CGRAM=2, side column Grams: an empty column that must
+    store a zero Gram, one full 64-row wave chunk, a 64 + 1 two-chunk column,
+    a three-chunk column); positive counts cycling through 1, 2, 31, 32, 33,
+    64, 65 and 257 (OCFFM_HOT=2: the 32-row batch edge, two full batches, a
+    row over HOT_CHUNK_MAX = 256 in two balanced chunks; OCFFM_CCG=2: the
+    columns' position counts cross the 256-position cut several times); 300
+    items (an id field and a one-node field of 5 uneven columns), item 0
+    positive for nine users in ten (the item half's hot row of two chunks)."""
+    rng = np.random.default_rng(17)
+    n = 300
+
+    def x():
+        return float(np.round(0.25 + 1.5 * rng.random(), 3))
+
+    feats, labels = [], []
+    for c, rows in enumerate(GRAM_EDGE_COLS):
+        for _ in range(rows):
+            i = len(feats)
+            feats.append([(0, c, x())])
+            cnt = GRAM_EDGE_POS[i % len(GRAM_EDGE_POS)]
+            if i % 10 == 0:
+                pos = 1 + rng.choice(n - 1, size=cnt, replace=False)
+            else:
+                pos = np.append(0, 1 + rng.choice(n - 1, size=cnt - 1, replace=False))
+            labels.append(np.sort(pos))
+    train = synth._build_rows(feats, labels)
+    cat = np.repeat(np.arange(5), (1, 64, 65, 40, 130))
+    item = synth._build_rows([[(0, j, 1.0), (1, int(cat[j]), x())] for j in range(n)], None)
+    return synth.Dataset("gram_edges", train, item, None, k=32,
+                         params=dict(k=32, t=20, l=4.0, w=0.0078125, r=-1.0))
+
+
+_HALF_REFS = {}
+
+
+def half_refs(name):
+    """(data set, [(f1, f2, half, gradient, v, Hessian-vector product)]) of
+    every half from the fp64 oracle, computed once per data set."""
+    if name not in _HALF_REFS:
+        ds = gram_edges() if name == "gram_edges" else synth.kkbox(**KK_RC)
+        o = O.Oracle(ds, with_test=False)
+        ocffm.srand(1)
+        o.init()
+        rng = np.random.default_rng(3)
+        refs = []
+        for f1 in range(o.f):
+            for f2 in range(f1, o.f):
+                for half in (0, 1):
+                    G0 = o.grad(f1, f2, half)
+                    v = rng.standard_normal(G0.size)
+                    refs.append((f1, f2, half, G0, v, o.hv(f1, f2, half, v)))
+        _HALF_REFS[name] = (ds, refs)
+    return _HALF_REFS[name]
+
+
+def check_halves(env, monkeypatch, precision, tol):
+    env = dict(env)
+    ds, refs = half_refs(env.pop("ds", "kk_rc"))
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    g = ocffm.problem_from_dataset(ds, precision=precision, with_test=False)
+    ocffm.srand(1)
+    g.init()
+    for f1, f2, half, G0, v, H0 in refs:
+        G1 = g.grad(f1, f2, half)
+        assert rel(G1, G0) <= tol, ("grad", f1, f2, half, rel(G1, G0))
+        H1 = g.hv(f1, f2, half, v)
+        assert rel(H1, H0) <= tol, ("hv", f1, f2, half, rel(H1, H0))
+
+
+def edge_envs(envs):
+    """The envs on gram_edges; ids like edges-CGRAM=2-NO_MFMA=1 (edges: no env)."""
+    return [pytest.param(dict(e, ds="gram_edges"), id="-".join(["edges"] + [f"{k[6:]}={v}" for k, v in e.items()]))
+            for e in envs]
+
+
+ENVS_FP32 = [{}, {"OCFFM_NO_MFMA": "1"}, {"OCFFM_CGRAM": "2"}, {"OCFFM_CGRAM": "2", "OCFFM_NO_MFMA": "1"},
+             {"OCFFM_TPRE": "1"}, {"OCFFM_HOT": "0"}, {"OCFFM_HOT": "2"}, {"OCFFM_HOT": "2", "OCFFM_NO_MFMA": "1"},
+             {"OCFFM_CCG": "2"}, {"OCFFM_CCG": "2", "OCFFM_NO_MFMA": "1"}]
+ENVS_FP64 = [{}, {"OCFFM_CGRAM": "2"}, {"OCFFM_CCG": "2"}, {"OCFFM_NO_MFMA": "1"}]
+
+
+@pytest.mark.parametrize("env", ENVS_FP32 + edge_envs(ENVS_FP32))
 def test_gradient_and_hv_fp32_k32(monkeypatch, env):
     """fp32 at k = 32 (the perf build: the cross halves' k x k Grams on MFMA,
     kernels.hpp k_gram_mfma32; OCFFM_CGRAM=2: every side half of a
-    one-node field on per-column Grams, built on MFMA by k_col_gram32 with
-    multi-chunk columns summed by k_gram_slot_sum, or by k_col_gram under
-    OCFFM_NO_MFMA) against the fp64 oracle: every half's gradient and
-    Hessian-vector product within 1e-4 of its largest entry."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    ds = synth.kkbox(**KK_RC)
-    o, g = pair(ds, precision=ocffm.FP32, with_test=False)
-    rng = np.random.default_rng(3)
-    for f1 in range(o.f):
-        for f2 in range(f1, o.f):
-            for half in (0, 1):
-                G0, G1 = o.grad(f1, f2, half), g.grad(f1, f2, half)
-                assert rel(G1, G0) <= 1e-4, ("grad", f1, f2, half, rel(G1, G0))
-                v = rng.standard_normal(G0.size)
-                H0, H1 = o.hv(f1, f2, half, v), g.hv(f1, f2, half, v)
-                assert rel(H1, H0) <= 1e-4, ("hv", f1, f2, half, rel(H1, H0))
+    one-node field on per-column Grams, built on MFMA by k_gram_build_mfma
+    with multi-chunk columns summed by k_gram_slot_sum, or by k_col_gram
+    under OCFFM_NO_MFMA) against the fp64 oracle: every half's gradient and
+    Hessian-vector product within 1e-4 of its largest entry.  On the kkbox
+    shape KK_RC, and (edges*) on gram_edges, the chunk boundaries of the Gram
+    builds."""
+    check_halves(env, monkeypatch, ocffm.FP32, 1e-4)
 
 
-@pytest.mark.parametrize("env", [{}, {"OCFFM_CGRAM": "2"}, {"OCFFM_CCG": "2"}, {"OCFFM_NO_MFMA": "1"}])
+@pytest.mark.parametrize("env", ENVS_FP64 + edge_envs(
+    ENVS_FP64 + [{"OCFFM_HOT": "2"}, {"OCFFM_CGRAM": "2", "OCFFM_NO_MFMA": "1"}]))
 def test_gradient_and_hv_fp64_k32(monkeypatch, env):
     """fp64 at k = 32, where the k x k work runs on the f64 matrix cores
     (v_mfma_f64_16x16x4f64: the cross-half aggregates k_gram_mfma_f64, the
-    side-half column Grams k_col_gram_f64 under OCFFM_CGRAM=2, the cross
-    column Grams k_hot_gram_mfma_f64 under OCFFM_CCG=2; OCFFM_NO_MFMA=1: the
-    VALU kernels): every half's gradient and Hessian-vector product within
-    1e-12 of the oracle's."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    ds = synth.kkbox(**KK_RC)
-    o, g = pair(ds, with_test=False)
-    rng = np.random.default_rng(3)
-    for f1 in range(o.f):
-        for f2 in range(f1, o.f):
-            for half in (0, 1):
-                G0, G1 = o.grad(f1, f2, half), g.grad(f1, f2, half)
-                assert rel(G1, G0) <= 1e-12, ("grad", f1, f2, half, rel(G1, G0))
-                v = rng.standard_normal(G0.size)
-                H0, H1 = o.hv(f1, f2, half, v), g.hv(f1, f2, half, v)
-                assert rel(H1, H0) <= 1e-12, ("hv", f1, f2, half, rel(H1, H0))
+    side-half column Grams under OCFFM_CGRAM=2 and the cross column Grams
+    under OCFFM_CCG=2 on k_gram_build_mfma; OCFFM_NO_MFMA=1: the VALU
+    kernels): every half's gradient and Hessian-vector product within 1e-12
+    of the oracle's.  On the kkbox shape KK_RC, and (edges*) on gram_edges,
+    the chunk boundaries of the Gram builds."""
+    check_halves(env, monkeypatch, ocffm.FP64, 1e-12)
 
 
 def test_epochs_fp32_k32():
@@ -347,7 +414,7 @@ def test_cfg5_shape_fp32_mfma(k, fu, hot, monkeypatch):
     1e-4 of their largest entry) on 2,000 rows (several row chunks per
     block of both kernels, ragged tails).  OCFFM_HOT=2: the item halves'
     popular items (and every row with >= 2 positives) on per-row Grams built
-    on MFMA (k_hot_gram_mfma, KP = 32 / 64; multi-chunk items summed in slot
+    on MFMA (k_gram_build_mfma, KP = 32 / 64; multi-chunk items summed in slot
     order)."""
     if hot:
         monkeypatch.setenv("OCFFM_HOT", hot)

@@ -16,6 +16,12 @@ import re
 import sys
 from collections import defaultdict
 
+# The Gram builds from gathered rows share their kernels, so a kernel name
+# separates fewer families than the library's profiler does: the builds with
+# Hessian weights (WtHess, k_col_gram) are col_gram and pair_gram together;
+# the list-weight builds are hot_gram and ccg_build together (as before);
+# and k_gram_slot_sum, which the library counts in the family of the build it
+# follows (col_gram and pair_gram included), is all counted as ccg_build here.
 FAMILY = [  # (regex on the demangled kernel name, family as named by the library's profiler)
     (r"k_hs_cross_seg", "hs_cross_row"), (r"k_hs_side_row", "hs_side_row"),
     (r"k_feat<\w+, \d+, 1\b", "feat_hv"), (r"k_feat<\w+, \d+, 0\b", "feat_grad"),
@@ -24,9 +30,9 @@ FAMILY = [  # (regex on the demangled kernel name, family as named by the librar
     (r"k_update_cross_seg", "update_cross_row"), (r"k_update_side_row", "update_side_row"),
     (r"k_gather_pos", "refresh_base"), (r"k_gram_part", "aggregates"), (r"k_reduce_parts", "aggr_reduce"),
     (r"k_gram_mfma32|k_gram_mfma64|k_gram_mfma_f64", "aggregates"), (r"k_rows_T", "rows_T"), (r"k_vec_sum", "bias_sum"), (r"k_pos_gram32|k_gram_rows", "aggregates"),
-    (r"k_hs_cross_rc", "hs_cross_row"), (r"k_col_gram", "col_gram"), (r"k_hv_cgram", "hv_cgram"),
+    (r"k_hs_cross_rc", "hs_cross_row"), (r"k_col_gram|k_gram_build\w*<.*WtHess", "col_gram"), (r"k_hv_cgram", "hv_cgram"),
     (r"k_apply", "apply_step"), (r"k_rowdot_multi", "rowdot_multi"), (r"k_colsum_multi", "aggregates"),
-    (r"k_cg_step", "cg_step"), (r"k_cg_r2", "cg_r2"), (r"k_hot_gram|k_gram_add_tau|k_hot_slot_sum", "ccg_build"),
+    (r"k_cg_step", "cg_step"), (r"k_cg_r2", "cg_r2"), (r"k_gram_build|k_gram_add_tau|k_gram_slot_sum", "ccg_build"),
     (r"k_hot_seg", "hot_seg"), (r"k_mask_rows", "mask_rows"), (r"k_sgd<", "k_sgd"), (r"k_phi<", "k_phi"),
     (r"k_feat_col<\w+, \d+, 1\b", "feat_hv"), (r"k_feat_col<\w+, \d+, 0\b", "feat_grad"),
     (r"k_feat_col<\w+, \d+, 2\b", "csc_scatter"), (r"k_cg_cgram", "cg_cgram"), (r"k_pg_step", "pg_step"),
