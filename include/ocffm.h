@@ -472,6 +472,97 @@ int ocffm_sgd_get(ocffm_sgd *s, char what, void *out, uint64_t cap, uint64_t *le
 int ocffm_sgd_set_w(ocffm_sgd *s, const float *w, uint64_t n);
 int ocffm_sgd_get_info(ocffm_sgd *s, ocffm_sgd_info *out);
 int ocffm_sgd_sync(ocffm_sgd *s);
+
+/* Top-N recommendation under the trainer's current W: the shape, order and
+ * rules of ocffm_problem_recommend on the SGD model.  Top-N items for rows
+ * [row0, row0+rows) of X; items: rows x topn, row-major; scores (may be NULL):
+ * the same shape.  Order: score descending, equal scores by ascending item
+ * index.  Does not change W or G.
+ * X: user rows in the train set's field space (read with the train Ds, as a
+ * test file is); their nodes are laid out as the train rows' are (global
+ * feature id = field offset + idx; field-major within a row, file order
+ * within a field).
+ *  - Scores: phi of ocffm_sgd_phi, decomposed so that no rows x n array is
+ *    built.  A node a of a row has feature j_a, field f_a, value x_a; user
+ *    fields are 0..fu-1, item fields fu..F-1; U_i the nodes of user row i,
+ *    V_j those of item row j; W[j][f] the kp-long row of feature j towards
+ *    field f.  Cross block c = f fv + (g - fu) for f < fu, g >= fu (the Newton
+ *    problem's order), C = fu fv:
+ *      P_c[i] = sum_{a in U_i, f_a = f} x_a W[j_a][g]
+ *      Q_c[j] = sum_{b in V_j, f_b = g} x_b W[j_b][f]
+ *      A_i    = sum_{a < a' in U_i} x_a x_a' <W[j_a][f_a'], W[j_a'][f_a]>
+ *      B_j    = the same sum over V_j
+ *      su_i   = sum_{a in U_i} x_a^2,   sv_j = sum_{b in V_j} x_b^2
+ *      s(i,j) = ((acc + B_j) + A_i) rn
+ *    acc: sum_c <P_c[i], Q_c[j]> in ocffm_problem_recommend's chain (chunks of
+ *    16 depth elements in order over the depth C kp); rn = 1 for a trainer
+ *    with norm = 0, else 1 / (su_i + sv_j) where that sum is > 0 and 1 where
+ *    it is 0.  All sums are fp32 in node order; the result is returned as
+ *    fp64.  In exact arithmetic this is phi: pairs of user nodes give A_i,
+ *    pairs of item nodes B_j, a user node in field f and an item node in
+ *    field g one term of <P_c[i], Q_c[j]>.  A feature that appears twice in
+ *    a row counts as two nodes, as in phi.
+ *  - Agreement with ocffm_sgd_phi: to fp32 rounding only, because phi sums
+ *    the same products in another order.
+ *  - Candidates: every item row j < V.m of every row.  With
+ *    OCFFM_REC_EXCLUDE_LABELS in flags, the row's own labels in X are excluded
+ *    (labels >= V.m are ignored, and so is the flag when X has no labels).
+ *  - No cold rows and no popularity fallback: a row without nodes has P = 0,
+ *    A = 0, su = 0 and is scored by B_j rn; an item row without nodes scores
+ *    A_i rn.
+ *  - Short rows: a row with fewer than topn candidates has OCFFM_REC_NONE and
+ *    a score of -inf in the remaining slots.
+ *  - Reproducibility: a (row, item) score has the same bits in this call, in
+ *    ocffm_sgd_label_ranks and between calls on an unchanged W, and does not
+ *    depend on the row's position in the call nor on how the call was chunked
+ *    or the items sliced (OCFFM_REC_ROWS, OCFFM_REC_SLICES, read at create):
+ *    the selection is on the total order (score, item index).
+ *  - The item side (Q_c, B, sv) is projected on the first serving call and
+ *    again only after W changed (ocffm_sgd_epoch, ocffm_sgd_average,
+ *    ocffm_sgd_set_w); the rows of X are projected per call.
+ *  - Errors: OCFFM_E_ARG for topn == 0, topn > OCFFM_REC_MAX_TOPN,
+ *    row0 + rows > X.m, NULL items, and for a trainer with no user field or no
+ *    item field (no cross block); OCFFM_E_DATA for a node of the call's rows
+ *    with fid >= fu or idx >= Ds[fid].  There is no OCFFM_E_STATE case: a
+ *    trainer always has a W.  rows == 0 is OCFFM_OK.
+ *  - Sharded trainers: every rank holds a whole W, so each rank serves the
+ *    rows it is given from its own current W; X is not sharded.  This has
+ *    only been run on one rank.
+ * Out of this path: candidate lists and pair scores (recommend_among, score)
+ * and fp64. */
+int ocffm_sgd_recommend(ocffm_sgd *s, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
+                        uint32_t flags, uint32_t *items, double *scores);
+/* Exact label ranks under the current W: ocffm_problem_label_ranks on the SGD
+ * model.  For every label of X its 0-based rank among the candidates of its
+ * row in ocffm_sgd_recommend's order, and (scores, may be NULL) the value
+ * ocffm_sgd_recommend returns for that (row, item), bit for bit; one entry per
+ * label in ocffm_data_get_labels order.  ncand (may be NULL): the candidate
+ * count of each of the X.m rows.
+ *  - Candidates of row i: every item j < V.m; with seen != NULL the labels of
+ *    seen's row i are removed (seen.m must equal X.m; its labels >= V.m are
+ *    ignored).  The other labels of the row count as candidates.
+ *  - Labels that are not candidates (>= V.m, or present in seen) get
+ *    OCFFM_RANK_NONE and a score of -inf.  Every copy of a duplicate label
+ *    gets the same rank and score.
+ *  - Arithmetic, reproducibility, the item-side cache and sharded trainers:
+ *    as ocffm_sgd_recommend.
+ *  - Errors: OCFFM_E_ARG for NULL ranks, an X without labels, seen.m != X.m,
+ *    or a trainer without a cross block; OCFFM_E_DATA for a node of X with
+ *    fid >= fu or idx >= Ds[fid].  X.m == 0 is OCFFM_OK. */
+int ocffm_sgd_label_ranks(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
+                          double *scores, uint32_t *ncand);
+/* ocffm_sgd_label_ranks followed by ocffm_eval_from_ranks (whose argument
+ * errors it shares: the cuts, NULL out). */
+int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
+                       uint32_t ncut, ocffm_eval *out);
+/* Serving counters; an unknown name reads 0 (as ocffm_problem_counter).
+ *  rank_item_builds    item-side projections since create
+ *  rank_setup_us       the last serving call's host set-up (the item-side
+ *                      projection included when it ran)
+ *  rank_item_build_us  the last item-side projection
+ *  rank_kernel_us      the last call's sweep, merge and label-score launches,
+ *                      between HIP events on the trainer's stream */
+int ocffm_sgd_counter(ocffm_sgd *s, const char *name, int64_t *value);
 void ocffm_sgd_destroy(ocffm_sgd *s);
 
 #ifdef __cplusplus

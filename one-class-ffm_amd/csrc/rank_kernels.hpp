@@ -1,6 +1,7 @@
 // rank_kernels.hpp — the serving kernels: top-N recommendation, ranking
-// evaluation, top-N among candidate lists.  Included by solver.hip only,
-// after kernels.hpp.
+// evaluation, top-N among candidate lists.  Included through rank_driver.hpp
+// by solver.hip (the block Newton-CG problem: NORM = false) and by sgd.hip
+// (the SGD trainer's model: NORM = true), after kernels.hpp.
 #pragma once
 
 #include "kernels.hpp"
@@ -50,6 +51,7 @@ template <typename real> struct SweepArgs {
   const double *popular;
   const int64_t *lptr;         // sorted, distinct items < n of each query row to leave out (exclude)
   const uint32_t *lcol;
+  const real *su, *sv;         // NORM: squared norms of the query rows, of the items
 };
 template <typename real> struct RecArgs : SweepArgs<real> {
   int topn;
@@ -132,6 +134,23 @@ __device__ __forceinline__ bool rec_in_sorted(const uint32_t *col, int64_t lo, i
   return lo < end && col[lo] == j;
 }
 
+// A pair's score from its chain's sum acc: (acc + b_j) + a_i; NORM (the SGD
+// model, sgd.hip): times rn = 1 / (su_i + sv_j), the instance's squared norm
+// (rn = 1 where that is 0: no node, or a model trained without the
+// normalisation, whose su and sv are zero).  The one text of the sweep and of
+// k_eval_label_scores, so a pair has the same bits in both.  The division is
+// correctly rounded: its result does not depend on the code around it.
+template <bool NORM, typename real>
+__device__ __forceinline__ real rec_score(real acc, real bj, real ai, real su, real sv) {
+  const real s = (acc + bj) + ai;
+  if constexpr (NORM) {
+    const real d = su + sv;
+    return s * (d > (real)0 ? (real)1 / d : (real)1);
+  } else {
+    return s;
+  }
+}
+
 // 4 consecutive depth elements of a row, and the MFMA of one of them
 template <typename real> struct RecMma;
 template <> struct RecMma<float> {
@@ -177,10 +196,11 @@ __device__ __forceinline__ typename RecMma<real>::V rec_ld(const real *const *T,
 // Every tile's scores go through sc; then consume(il, i, j, v, cand) runs once
 // per row of this wave (row il of the tile, i of the launch) with the lane's
 // item j, its score v and whether it is a candidate so far: inside the slice
-// and, for a cold row, below npop.  Block-uniform call, after a barrier that
+// and, for a cold row, below npop (NORM: no row is cold, g.cold and
+// g.popular are not read).  Block-uniform call, after a barrier that
 // covers the caller's own LDS set-up; what consume writes to LDS for another
 // tile's call of the same row needs no barrier of its own.
-template <typename real, int KP, typename F>
+template <typename real, int KP, bool NORM, typename F>
 __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0, uint64_t sl,
                                           double (&sc)[REC_RT][REC_IT + 1], F &&consume) {
   using M = RecMma<real>;
@@ -194,20 +214,22 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
   // this lane's A rows (row m of each half); the side terms of its D rows
   const uint64_t ra0 = r0 + m, ra1 = r0 + 16 + m;
   const bool ha0 = ra0 < g.R, ha1 = ra1 < g.R;
-  real ai[2][4];
+  real ai[2][4], sui[2][4];
 #pragma unroll
   for (int h = 0; h < 2; h++)
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const uint64_t i = r0 + 16 * h + M::drow(q, r);
       ai[h][r] = i < g.R ? g.a[i] : (real)0;
+      sui[h][r] = (NORM && i < g.R) ? g.su[i] : (real)0;
     }
   // the selection's rows of this wave: REC_RT / 4 of them, cold flags as bits
   unsigned coldbits = 0;
-  for (int rr = 0; rr < REC_RT / 4; rr++) {
-    const uint64_t i = r0 + w * (REC_RT / 4) + rr;
-    if (i < g.R && g.cold[i]) coldbits |= 1u << rr;
-  }
+  if constexpr (!NORM)
+    for (int rr = 0; rr < REC_RT / 4; rr++) {
+      const uint64_t i = r0 + w * (REC_RT / 4) + rr;
+      if (i < g.R && g.cold[i]) coldbits |= 1u << rr;
+    }
   const V zero = {(real)0, (real)0, (real)0, (real)0};
   uint64_t jq = jb + (uint64_t)w * 16 + m;  // this lane's B row (item) of the tile being loaded
   bool hb = jq < je;
@@ -242,6 +264,7 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
   for (uint64_t t0 = jb; t0 < je; t0 += REC_IT) {
     V acc0 = zero, acc1 = zero;
     const real bj = hb ? g.b[jq] : (real)0;
+    const real svj = (NORM && hb) ? g.sv[jq] : (real)0;
     for (int c0 = 0; c0 < nch; c0 += 2 * GR) {
       load(std::integral_constant<int, 1>(), c0 + GR);
       mma(std::integral_constant<int, 0>(), c0, acc0, acc1);
@@ -256,8 +279,8 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int i0 = M::drow(q, r);
-      sc[i0][w * 16 + m] = (double)((acc0[r] + bj) + ai[0][r]);
-      sc[16 + i0][w * 16 + m] = (double)((acc1[r] + bj) + ai[1][r]);
+      sc[i0][w * 16 + m] = (double)rec_score<NORM>(acc0[r], bj, ai[0][r], sui[0][r], svj);
+      sc[16 + i0][w * 16 + m] = (double)rec_score<NORM>(acc1[r], bj, ai[1][r], sui[1][r], svj);
     }
     __syncthreads();
     // wave w takes rows 8 w .. 8 w + 7, lane = the tile's item
@@ -280,7 +303,7 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
   }
 }
 
-template <typename real, int KP>
+template <typename real, int KP, bool NORM = false>
 __global__ __launch_bounds__(BLOCK) void k_rec_topn(RecArgs<real> g) {
   __shared__ double sc[REC_RT][REC_IT + 1];
   __shared__ double lv[REC_RT][REC_MAX];
@@ -301,7 +324,7 @@ __global__ __launch_bounds__(BLOCK) void k_rec_topn(RecArgs<real> g) {
   }
   __syncthreads();
   // selection: the threshold first, so the search runs on few candidates
-  rec_sweep<real, KP>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
+  rec_sweep<real, KP, NORM>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
     double tv = thr_v[il];
     uint32_t tj = thr_j[il];
     cand = cand && rec_better(v, (uint32_t)j, tv, tj);
@@ -383,10 +406,10 @@ static __global__ __launch_bounds__(BLOCK) void k_rec_merge(uint64_t R, int S, i
 //
 // k_eval_label_scores: a wave takes 16 (row, item) pairs; lane l holds the
 // operands of pair l & 15 on both sides of the MFMA and runs k_rec_topn's
-// chain (chunks of 16 depth elements in order, then (acc + b_j) + a_i), so the
+// chain (chunks of 16 depth elements in order, then rec_score), so the
 // diagonal of the 16 x 16 product holds each pair's score with the bits the
 // sweep gives it: an output element depends only on its own row and item.
-template <typename real, int KP>
+template <typename real, int KP, bool NORM = false>
 __global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, const real *const *__restrict__ P,
                                                              const real *const *__restrict__ Q,
                                                              const real *__restrict__ a, const real *__restrict__ b,
@@ -394,7 +417,9 @@ __global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, 
                                                              const double *__restrict__ popular,
                                                              const uint32_t *__restrict__ lrow,
                                                              const uint32_t *__restrict__ litem,
-                                                             double *__restrict__ out) {
+                                                             double *__restrict__ out,
+                                                             const real *__restrict__ su,
+                                                             const real *__restrict__ sv) {
   using M = RecMma<real>;
   using V = typename M::V;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -412,7 +437,10 @@ __global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, 
   if (!have) return;
 #pragma unroll
   for (int r = 0; r < 4; r++)
-    if (M::drow(q, r) == m) out[e] = cold[row] ? popular[item] : (double)((acc[r] + b[item]) + a[row]);
+    if (M::drow(q, r) == m) {
+      if constexpr (NORM) out[e] = (double)rec_score<true>(acc[r], b[item], a[row], su[row], sv[item]);
+      else out[e] = cold[row] ? popular[item] : (double)rec_score<false>(acc[r], b[item], a[row], (real)0, (real)0);
+    }
 }
 
 // k_eval_count: k_rec_topn's sweep (rec_sweep: one text, hence the same bits
@@ -439,7 +467,7 @@ template <typename real> struct EvalArgs : SweepArgs<real> {  // (lptr / lcol: t
   uint32_t *cnt;               // per label: candidates between the label before it and itself
 };
 
-template <typename real, int KP>
+template <typename real, int KP, bool NORM = false>
 __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
   __shared__ double sc[REC_RT][REC_IT + 1];
   __shared__ uint32_t cnt[REC_RT][EV_CAP];
@@ -477,7 +505,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
     if (!any) return;
   }
   // counting: the last label first, so the search runs on few candidates
-  rec_sweep<real, KP>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
+  rec_sweep<real, KP, NORM>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
     const int np = kn[il];
     if (np == 0) return;
     cand = cand && rec_better(v, (uint32_t)j, last_v[il], last_j[il]);

@@ -21,7 +21,9 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <map>
 #include <memory>
 #include <type_traits>
 #include <cstdint>
@@ -35,6 +37,7 @@
 #include "common.hpp"
 #include "host_data.h"
 #include "kernels.hpp"
+#include "rank_driver.hpp"
 
 namespace ocffm {
 namespace sgd {
@@ -291,6 +294,79 @@ __global__ __launch_bounds__(256) void k_phi(Args d, uint64_t npairs_in, const u
   }
 }
 
+// ------------------------------------------------------------ serving ---
+// The model in the serving sweeps' form (rank_kernels.hpp; ocffm.h
+// ocffm_sgd_recommend states the decomposition).  For user fields f < fu and
+// item fields g >= fu, cross block c = f fv + (g - fu):
+//   user rows:  P_c[i] = sum_{a in U_i, f_a = f} x_a W[j_a][g]
+//   item rows:  Q_c[j] = sum_{b in V_j, f_b = g} x_b W[j_b][f]
+// so that <P_c[i], Q_c[j]> summed over c is phi's sum over the pairs of one
+// user node and one item node; the pairs within one row are its side term
+// (A_i or B_j: k_phi's pair loop restricted to the row), and sum x^2 its
+// squared norm (stored as 0 for a model trained without the normalisation:
+// rec_score then multiplies by 1).
+//
+// k_project: one subgroup of LPR lanes per (row, c), c <= C; c < C: the table
+// row P_c[row] / Q_c[row], 16 B of the W rows per lane, summed over the row's
+// nodes in node order; c == C: the side term over the row's node pairs
+// (a < a') in order, and the squared norm in node order.  A row's sums are
+// one subgroup's, in the row's own order: they do not depend on where the row
+// sits in the launch.  Rows of any width (the node list is walked, not held
+// in lanes).  Algorithmic bytes: the row's nodes, one KP-float W row per
+// (node, opposite field) and per ordered node pair, C KP + 2 floats out.
+struct ProjArgs {
+  uint64_t rows;
+  uint32_t F, fu, fv;
+  int item, norm;           // item: the rows are item rows (Q_c); norm: store the squared norms
+  const uint64_t *ptr;      // the rows' node lists (Trainer::build_nodes' layout)
+  const uint32_t *node, *fld;
+  const float *val;
+  const float *W;
+  float *const *T;          // C tables, rows x KP
+  float *side, *sq;         // per row
+};
+
+template <int KP>
+__global__ __launch_bounds__(256) void k_project(ProjArgs d) {
+  using Gm = Geo<float, KP>;
+  constexpr int LPR = Gm::LPR;
+  const int li = threadIdx.x % LPR;
+  const uint32_t C = d.fu * d.fv;
+  const size_t F = d.F;
+  const uint64_t total = d.rows * (C + 1);
+  const uint64_t nsg = (uint64_t)gridDim.x * blockDim.x / LPR;
+  for (uint64_t sg = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPR; sg < total; sg += nsg) {
+    const uint64_t row = sg / (C + 1);
+    const uint32_t c = (uint32_t)(sg % (C + 1));
+    const uint64_t pb = d.ptr[row], pe = d.ptr[row + 1];
+    if (c < C) {
+      const uint32_t f = c / d.fv, g = d.fu + c % d.fv;
+      const uint32_t own = d.item ? g : f, to = d.item ? f : g;
+      f4v acc = vzero<float>();
+      for (uint64_t p = pb; p < pe; p++)
+        if (d.fld[p] == own)
+          acc += vsplat<float>(d.val[p]) * vld<float>(d.W + ((size_t)d.node[p] * F + to) * KP + li * 4);
+      vst<float>(d.T[c] + row * KP + li * 4, acc);
+    } else {
+      float s = 0, q = 0;
+      for (uint64_t a = pb; a < pe; a++) {
+        const uint32_t ja = d.node[a], fa = d.fld[a];
+        const float xa = d.val[a];
+        q += xa * xa;
+        for (uint64_t b = a + 1; b < pe; b++) {
+          const f4v wa = vld<float>(d.W + ((size_t)ja * F + d.fld[b]) * KP + li * 4);
+          const f4v wb = vld<float>(d.W + ((size_t)d.node[b] * F + fa) * KP + li * 4);
+          s += sg_sum<LPR>(hsum<float>(wa * wb)) * (xa * d.val[b]);
+        }
+      }
+      if (li == 0) {
+        d.side[row] = s;
+        d.sq[row] = d.norm ? q : 0.0f;
+      }
+    }
+  }
+}
+
 // W (and G) /= ranks after the all-reduce (model averaging).
 __global__ void k_scale(uint64_t n, float *x, float s) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
@@ -326,6 +402,14 @@ class Trainer {
     std::vector<uint64_t> off(F_ + 1, 0);
     for (uint32_t f = 0; f < F_; f++) off[f + 1] = off[f] + (f < fu_ ? U.Ds[f] : V.Ds[f - fu_]);
     nf_ = off[F_];
+    off_ = off;
+    if (const char *e = std::getenv("OCFFM_REC_SLICES")) rec_slices_ = (unsigned)std::clamp(std::atoi(e), 1, 256);
+    if (const char *e = std::getenv("OCFFM_REC_ROWS")) rec_rows_ = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    {
+      int ncu = 0;
+      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, prm.device) != hipSuccess) ncu = 1;
+      ncu_ = (unsigned)std::max(1, ncu);
+    }
     if (nf_ >= (1ull << 32)) throw Error(OCFFM_E_DATA, "more than 2^32 features");
     int umax = 0, vmax = 0;
     build_nodes(U, 0, off, uptr_, unode_, ufld_, uval_, umax);
@@ -437,6 +521,7 @@ class Trainer {
     HIPCHK(hipMemcpyAsync(&loss, loss_.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     epoch_++;
+    version_++;
     return T_ ? loss / (double)T_ : 0.0;
   }
 
@@ -444,6 +529,7 @@ class Trainer {
   // With a host hook (tests on one GPU) the sums go through host memory.
   void average() {
     if (!nccl_ && !host_fn_) return;
+    version_++;
     const size_t nw = (size_t)nf_ * F_ * kp_;
     if (host_fn_) {
       std::vector<float> hb(nw);
@@ -512,6 +598,7 @@ class Trainer {
   void set_w(const float *w, uint64_t n) {
     if (n != (uint64_t)nf_ * F_ * kp_) throw Error(OCFFM_E_ARG, "size mismatch");
     HIPCHK(hipMemcpy(W_.p, w, n * 4, hipMemcpyHostToDevice));
+    version_++;
   }
   void info(ocffm_sgd_info *o) const {
     o->n_features = nf_;
@@ -522,7 +609,181 @@ class Trainer {
   }
   void sync() { HIPCHK(hipStreamSynchronize(stream_)); }
 
+  // ------------------------------------------------------------ serving
+  // Top-N items and exact label ranks under the current W (ocffm.h
+  // ocffm_sgd_recommend, ocffm_sgd_label_ranks): the query rows of X are laid
+  // out as build_nodes lays out the train rows and projected (k_project); the
+  // item side is projected once per model version; the serving sweeps' driver
+  // (rank_driver.hpp) does the rest, as it does for the Newton problem.
+  void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
+                 double *scores) {
+    serve_check();
+    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
+    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
+    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    check_rows(X, row0, rows);
+    if (rows == 0) return;
+    serve_begin();
+    const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
+    Query L;
+    layout(L, X, row0, rows, excl ? &X : nullptr);
+    const RankModel<float> m = model();
+    Rank{*this, m}.recommend(L, rows, topn, excl, items, scores, "rank_setup_us");
+    counters_["rank_kernel_us"] = (int64_t)kernel_us_;
+  }
+  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores, uint32_t *ncand) {
+    serve_check();
+    if (!ranks) throw Error(OCFFM_E_ARG, "null ranks");
+    if (!X.has_label || X.yptr.size() != X.m + 1) throw Error(OCFFM_E_ARG, "X has no labels");
+    if (seen && (seen->m != X.m || (seen->m && seen->yptr.size() != seen->m + 1)))
+      throw Error(OCFFM_E_ARG, "seen must have X's row count (and labels)");
+    if (X.m >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many rows");
+    check_rows(X, 0, X.m);
+    if (X.m == 0) return;
+    serve_begin();
+    Query L;
+    layout(L, X, 0, X.m, seen);
+    const RankModel<float> m = model();
+    Rank{*this, m}.label_ranks(L, X, seen != nullptr, ranks, scores, ncand, "rank_setup_us");
+    counters_["rank_kernel_us"] = (int64_t)kernel_us_;
+  }
+  int64_t counter(const char *name) const {
+    const auto it = counters_.find(name);
+    return it == counters_.end() ? 0 : it->second;
+  }
+
  private:
+  // One side's rows in the sweeps' form: C tables (rows x KP), side terms, squared norms
+  struct Proj {
+    DevBuf<float> tab, side, sq;
+    DevBuf<float *> tp;
+  };
+  void project(Proj &o, uint64_t rows, bool item, const uint64_t *ptr, const uint32_t *node, const uint32_t *fld,
+               const float *val) {
+    const uint32_t C = fu_ * fv_;
+    o.tab.alloc(std::max<size_t>(1, (size_t)C * rows * kp_), false);
+    o.side.alloc(std::max<uint64_t>(1, rows), false);
+    o.sq.alloc(std::max<uint64_t>(1, rows), false);
+    std::vector<float *> tl(C);
+    for (uint32_t c = 0; c < C; c++) tl[c] = o.tab.p + (size_t)c * rows * kp_;
+    o.tp.upload(tl);
+    if (rows == 0) return;
+    ProjArgs a{rows, F_, fu_, fv_, item ? 1 : 0, prm_.norm ? 1 : 0, ptr, node, fld, val, W_.p, o.tp.p, o.side.p, o.sq.p};
+    const uint64_t threads = rows * (C + 1) * (kp_ / 4);
+    const unsigned grid = (unsigned)std::min<uint64_t>((threads + 255) / 256, 1u << 20);
+    launch_kp([&](auto K) { hipLaunchKernelGGL(k_project<decltype(K)::value>, grid, 256, 0, stream_, a); });
+    HIPCHK(hipGetLastError());
+  }
+  // The query rows of a call: their nodes, projection and exclusion lists
+  struct Query : RankRows<float> {
+    Proj pr;
+    DevBuf<uint64_t> ptr;
+    DevBuf<uint32_t> node, fld;
+    DevBuf<float> val;
+  };
+  void serve_check() const {
+    if (fu_ == 0 || fv_ == 0) throw Error(OCFFM_E_ARG, "no user field or no item field: the model has no cross block");
+  }
+  void check_rows(const HostData &X, uint64_t row0, uint64_t rows) const {
+    for (uint64_t p = X.raw.xptr[row0]; p < X.raw.xptr[row0 + rows]; p++)
+      if (X.raw.fid[p] >= fu_ || X.raw.idx[p] >= off_[X.raw.fid[p] + 1] - off_[X.raw.fid[p]])
+        throw Error(OCFFM_E_DATA, "X has a node with fid >= the train user fields or idx >= Ds[fid] (read it with the train Ds)");
+  }
+  // The call's clock starts; the item side follows the model
+  void serve_begin() {
+    sync();
+    rank_t0_ = std::chrono::steady_clock::now();
+    kernel_us_ = 0;
+    if (item_version_ == version_) return;
+    project(item_, n_items_, true, vptr_.p, vnode_.p, vfld_.p, vval_.p);
+    sync();
+    item_version_ = version_;
+    counters_["rank_item_builds"]++;
+    counters_["rank_item_build_us"] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rank_t0_).count();
+  }
+  void layout(Query &L, const HostData &X, uint64_t row0, uint64_t rows, const HostData *lab) {
+    // field-major within a row, file order within a field (build_nodes)
+    std::vector<uint64_t> p(rows + 1, 0);
+    std::vector<uint32_t> nd, fd;
+    std::vector<float> vl;
+    for (uint64_t i = 0; i < rows; i++) {
+      for (uint32_t f = 0; f < fu_; f++)
+        for (uint64_t t = X.raw.xptr[row0 + i]; t < X.raw.xptr[row0 + i + 1]; t++)
+          if (X.raw.fid[t] == f) {
+            nd.push_back((uint32_t)(off_[f] + X.raw.idx[t]));
+            fd.push_back(f);
+            vl.push_back((float)X.raw.val[t]);
+          }
+      p[i + 1] = nd.size();
+    }
+    L.ptr.upload(p);
+    L.node.upload(nd.empty() ? std::vector<uint32_t>{0} : nd);
+    L.fld.upload(fd.empty() ? std::vector<uint32_t>{0} : fd);
+    L.val.upload(vl.empty() ? std::vector<float>{0} : vl);
+    project(L.pr, rows, false, L.ptr.p, L.node.p, L.fld.p, L.val.p);
+    L.P = L.pr.tp.p;
+    L.a = L.pr.side.p;
+    L.su = L.pr.sq.p;
+    L.cold.assign(rows, 0);  // (no row is cold in this mode)
+    L.dcold.upload(L.cold);
+    L.exclusions(lab, row0, rows, n_items_);
+  }
+  RankModel<float> model() const {
+    RankModel<float> m;
+    m.Q = item_.tp.p;
+    m.b = item_.side.p;
+    m.sv = item_.sq.p;
+    m.n = m.npop = n_items_;
+    m.C = fu_ * fv_;
+    m.kp = kp_;
+    m.slices = rec_slices_;
+    m.chunk_rows = rec_rows_;
+    m.stream = stream_;
+    return m;
+  }
+  // What the driver needs of its host (rank_driver.hpp); the timing hook sums
+  // the launches' time between HIP events on the trainer's stream
+  using Rank = RankDriver<float, true, Trainer>;
+  friend Rank;
+  template <typename... KArgs, typename... A>
+  void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t smem, A... a) {
+    static_assert(sizeof...(KArgs) == sizeof...(A), "kernel argument count");
+    hipLaunchKernelGGL(k, grid, block, (uint32_t)smem, stream_, static_cast<KArgs>(a)...);
+    HIPCHK(hipGetLastError());
+  }
+  template <class L> void prof_launch(const char *, double, L &&body, double = 0) {
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    pending_.push_back({a, b});
+    HIPCHK(hipEventRecord(a, stream_));
+    body();
+    HIPCHK(hipEventRecord(b, stream_));
+  }
+  void flush_prof() {
+    sync();
+    for (auto &e : pending_) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+      kernel_us_ += 1e3 * ms;
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    pending_.clear();
+  }
+  template <typename... KArgs> unsigned resident(void (*k)(KArgs...), size_t smem) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), BLOCK, smem) !=
+            hipSuccess || nb <= 0)
+      nb = 1;
+    return (unsigned)nb * ncu_;
+  }
+  void rank_setup_done(const char *counter) {
+    counters_[counter] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rank_t0_).count();
+  }
+
   template <class L> void launch_kp(L &&l) {
     switch (kp_) {
       case 4: l(std::integral_constant<int, 4>{}); break;
@@ -633,6 +894,18 @@ class Trainer {
   DevBuf<double> loss_;
   std::vector<float> h_prob_;
   std::vector<uint32_t> h_alias_;
+  // serving
+  std::vector<uint64_t> off_;      // first global feature id of each field
+  unsigned rec_slices_ = 0;        // OCFFM_REC_SLICES (0: from n, the rows and the CU count)
+  uint64_t rec_rows_ = 0;          // OCFFM_REC_ROWS (0: 4096 rows per chunk)
+  unsigned ncu_ = 1;
+  uint64_t version_ = 1;           // of W: epoch, average and set_w advance it
+  uint64_t item_version_ = 0;      // the version item_ was projected from
+  Proj item_;                      // Q_c, B_j, sv_j
+  std::map<std::string, int64_t> counters_;  // ocffm_sgd_counter
+  std::chrono::steady_clock::time_point rank_t0_;
+  double kernel_us_ = 0;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_;
 };
 
 }  // namespace sgd
@@ -703,6 +976,40 @@ int ocffm_sgd_get(ocffm_sgd *s, char what, void *out, uint64_t cap, uint64_t *le
 int ocffm_sgd_set_w(ocffm_sgd *s, const float *w, uint64_t n) { SGD_CALL(s->t->set_w(w, n)); }
 int ocffm_sgd_get_info(ocffm_sgd *s, ocffm_sgd_info *out) { SGD_CALL(s->t->info(out)); }
 int ocffm_sgd_sync(ocffm_sgd *s) { SGD_CALL(s->t->sync()); }
+int ocffm_sgd_recommend(ocffm_sgd *s, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags,
+                        uint32_t *items, double *scores) {
+  SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X"); s->t->recommend(X->d, row0, rows, topn, flags, items, scores));
+}
+int ocffm_sgd_label_ranks(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks, double *scores,
+                          uint32_t *ncand) {
+  SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X");
+           s->t->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand));
+}
+int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut,
+                       ocffm_eval *out) {
+  std::vector<uint32_t> ranks, ncand;
+  std::vector<double> scores;
+  const int st = guarded([&] {
+    if (!s || !s->t) throw ocffm::Error(OCFFM_E_ARG, "null SGD trainer");
+    if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X");
+    if (!out) throw ocffm::Error(OCFFM_E_ARG, "null output");
+    // (ocffm_eval_from_ranks checks the cuts: an empty file puts that before the ranking)
+    const uint64_t none = 0;
+    const uint32_t nc0 = 0;
+    if (const int c = ocffm_eval_from_ranks(0, &none, nullptr, nullptr, &nc0, cuts, ncut, out))
+      throw ocffm::Error(c, ocffm_last_error());
+    const ocffm::HostData &d = X->d;
+    ranks.resize(d.ycol.size() + 1);
+    ncand.resize(d.m + 1);
+    scores.resize(d.ycol.size() + 1);
+    s->t->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data());
+  });
+  if (st != OCFFM_OK) return st;
+  return ocffm_eval_from_ranks(X->d.m, X->d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+}
+int ocffm_sgd_counter(ocffm_sgd *s, const char *name, int64_t *value) {
+  SGD_CALL(if (!name || !value) throw ocffm::Error(OCFFM_E_ARG, "null argument"); *value = s->t->counter(name));
+}
 void ocffm_sgd_destroy(ocffm_sgd *s) { delete s; }
 
 }  // extern "C"

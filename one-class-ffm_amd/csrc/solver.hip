@@ -37,7 +37,7 @@
 #include "devbuild.h"
 #include "host_data.h"
 #include "kernels.hpp"
-#include "rank_kernels.hpp"
+#include "rank_driver.hpp"
 
 namespace ocffm {
 
@@ -49,26 +49,6 @@ static uint32_t pad_k(uint32_t k) {
   uint32_t kp = 4;
   while (kp < k) kp <<= 1;
   return kp;
-}
-
-// OCFFM_EXP_KP32 (experiment builds only, tools/build_variant.sh): fp32 at
-// KP = 32 instantiated alone, so a kernel experiment compiles in a fraction
-// of the full build's time.
-template <class F> static void with_kp(uint32_t kp, F &&f) {
-#ifdef OCFFM_EXP_KP32
-  if (kp != 32) throw Error(OCFFM_E_ARG, "experiment build: k must pad to 32");
-  f(std::integral_constant<int, 32>());
-  return;
-#endif
-  switch (kp) {
-    case 4: f(std::integral_constant<int, 4>()); break;
-    case 8: f(std::integral_constant<int, 8>()); break;
-    case 16: f(std::integral_constant<int, 16>()); break;
-    case 32: f(std::integral_constant<int, 32>()); break;
-    case 64: f(std::integral_constant<int, 64>()); break;
-    case 128: f(std::integral_constant<int, 128>()); break;
-    default: throw Error(OCFFM_E_ARG, "k must be in 1..128");
-  }
 }
 
 static unsigned grid_for(uint64_t items, uint64_t per_block, unsigned cap = 4096) {
@@ -1032,17 +1012,11 @@ template <typename real> class Problem final : public ProblemBase {
   // train Ds), the projections P_c through utx, a_i, the cold flags, and the
   // sorted distinct items < n of each row of `lab` (the labels to leave out;
   // NULL: none).
-  struct RecRows {
+  struct RecRows : RankRows<real> {  // (the driver's view: P = pt, a = ax)
     DevSide<real> Xs;
     std::vector<DevBuf<real>> Px;
     DevBuf<real *> pt;
     DevBuf<real> ax;  // a_i (zero without the side blocks)
-    std::vector<uint8_t> cold;
-    DevBuf<uint8_t> dcold;
-    std::vector<int64_t> lptr;
-    std::vector<uint32_t> lcol;
-    DevBuf<int64_t> dlptr;
-    DevBuf<uint32_t> dlcol;
   };
   void rec_check(const HostData &X, uint64_t row0, uint64_t rows) {
     if (X.f > fu_) throw Error(OCFFM_E_ARG, "X has more fields than the train set's user side");
@@ -1085,20 +1059,31 @@ template <typename real> class Problem final : public ProblemBase {
     L.cold.resize(rows);
     for (uint64_t i = 0; i < rows; i++) L.cold[i] = X.nnx[row0 + i] == 0;
     L.dcold.upload(L.cold);
-    L.lptr.assign(rows + 1, 0);
-    L.lcol.clear();
-    if (lab)
-      for (uint64_t i = 0; i < rows; i++) {
-        const size_t b = L.lcol.size();
-        for (uint64_t p = lab->yptr[row0 + i]; p < lab->yptr[row0 + i + 1]; p++)
-          if (lab->ycol[p] < n_) L.lcol.push_back((uint32_t)lab->ycol[p]);
-        std::sort(L.lcol.begin() + b, L.lcol.end());
-        L.lcol.erase(std::unique(L.lcol.begin() + b, L.lcol.end()), L.lcol.end());
-        L.lptr[i + 1] = (int64_t)L.lcol.size();
-      }
-    if (L.lcol.empty()) L.lcol.push_back(0);
-    L.dlptr.upload(L.lptr);
-    L.dlcol.upload(L.lcol);
+    L.exclusions(lab, row0, rows, n_);
+    L.P = L.pt.p;
+    L.a = L.ax.p;
+  }
+  // The serving sweeps' driver (rank_driver.hpp) on this problem's item side
+  using Rank = RankDriver<real, false, Problem>;
+  friend Rank;
+  RankModel<real> rank_model() {
+    RankModel<real> m;
+    m.Q = tabs_.p + C_;
+    m.b = V_.bias.p;
+    m.popular = popular_.p;
+    m.n = n_;
+    m.npop = std::min<uint64_t>(npop_, n_);
+    m.C = C_;
+    m.kp = kp_;
+    m.slices = rec_slices_;
+    m.chunk_rows = rec_rows_;
+    m.stream = stream_;
+    return m;
+  }
+  std::chrono::steady_clock::time_point rank_t0_;  // the serving call's start
+  void rank_setup_done(const char *counter) {
+    counters[counter] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rank_t0_).count();
   }
   // The top-N calls' common arguments
   void rec_check_topn(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, const uint32_t *items) {
@@ -1106,92 +1091,10 @@ template <typename real> class Problem final : public ProblemBase {
     if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
     if (!items) throw Error(OCFFM_E_ARG, "null items");
   }
-  // Resident blocks of a kernel with a KP parameter (kernel_of(K): its instantiation)
-  template <class KOf> unsigned rec_resident(KOf &&kernel_of) {
-    unsigned slots = 0;
-    with_kp(kp_, [&](auto K) { slots = resident(kernel_of(K), 0); });
-    return slots;
-  }
-  uint64_t rec_chunk(uint64_t rows) const { return std::min<uint64_t>(rows, rec_rows_ ? rec_rows_ : 4096); }
-  // Row chunk and item slices of a sweep (k_rec_topn, k_eval_count)
-  struct RecPlan {
-    uint64_t chunk, S, per;  // rows per launch; item slices; items per slice (multiple of REC_IT)
-  };
-  template <class KOf> RecPlan rec_plan(uint64_t rows, KOf &&kernel_of) {
-    RecPlan p;
-    p.chunk = rec_chunk(rows);
-    p.S = rec_slices_;
-    if (!p.S) {
-      // one resident wave of blocks: every slice costs each row its own
-      // list warm-up (~topn inserts), so as few slices as fill the machine;
-      // at least 4 item tiles per slice
-      p.S = std::max<uint64_t>(1, rec_resident(kernel_of) / ((p.chunk + REC_RT - 1) / REC_RT));
-      p.S = std::min<uint64_t>(p.S, (n_ + 4 * REC_IT - 1) / (4 * REC_IT));
-      p.S = std::clamp<uint64_t>(p.S, 1, 64);
-    }
-    p.per = ((n_ + p.S - 1) / p.S + REC_IT - 1) / REC_IT * REC_IT;
-    return p;
-  }
-  // A sweep's arguments for rows [c0, c0 + cr) of L
-  void rec_sweep_args(SweepArgs<real> &g, const RecRows &L, uint64_t c0, uint64_t cr, const RecPlan &p, bool exclude) {
-    g.R = cr;
-    g.p0 = c0;
-    g.n = n_;
-    g.npop = std::min<uint64_t>(npop_, n_);
-    g.per = p.per;
-    g.C = (int)C_;
-    g.exclude = exclude ? 1 : 0;
-    g.S = (uint32_t)p.S;
-    g.rt = (uint32_t)((cr + REC_RT - 1) / REC_RT);
-    g.P = L.pt.p;
-    g.Q = tabs_.p + C_;
-    g.a = L.ax.p + c0;
-    g.b = V_.bias.p;
-    g.cold = L.dcold.p + c0;
-    g.popular = popular_.p;
-    g.lptr = L.dlptr.p + c0;
-    g.lcol = L.dlcol.p;
-  }
-  // Scores of the pairs (krow[e] of L, kitem[e]), every one a candidate, timed under `family`
-  std::vector<double> score_pairs(const RecRows &L, const std::vector<uint32_t> &krow,
-                                  const std::vector<uint32_t> &kitem, const char *family) {
-    const uint64_t nk = kitem.size();
-    DevBuf<uint32_t> dkrow, dkitem;
-    DevBuf<double> dkv;
-    dkrow.upload(krow);
-    dkitem.upload(kitem);
-    dkv.alloc(nk, false);
-    const double depth = (double)C_ * kp_;
-    prof_launch(family, (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
-      with_kp(kp_, [&](auto K) {
-        constexpr int KP = decltype(K)::value;
-        launch(k_eval_label_scores<real, KP>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)C_,
-               (const real *const *)L.pt.p, (const real *const *)(tabs_.p + C_), (const real *)L.ax.p,
-               (const real *)V_.bias.p, (const uint8_t *)L.dcold.p, (const double *)popular_.p,
-               (const uint32_t *)dkrow.p, (const uint32_t *)dkitem.p, dkv.p);
-      });
-    }, 2.0 * (double)nk * depth);
-    std::vector<double> kv(nk);
-    HIPCHK(hipMemcpyAsync(kv.data(), dkv.p, nk * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    sync();
-    return kv;
-  }
-  // A chunk's results (rows c0.. of the call) to the caller's arrays
-  void rec_copy_back(uint64_t c0, uint64_t cr, uint32_t topn, const DevBuf<uint32_t> &out_j, const DevBuf<double> &out_v,
-                     uint32_t *items, double *scores) {
-    HIPCHK(hipMemcpyAsync(items + c0 * topn, out_j.p, cr * topn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-    if (scores)
-      HIPCHK(hipMemcpyAsync(scores + c0 * topn, out_v.p, cr * topn * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    sync();
-  }
-
   // ------------------------------------------------- ranking evaluation
   // Exact rank of every label of X among its row's candidates (ocffm.h
-  // ocffm_problem_label_ranks).  The distinct candidate labels of every row
-  // are scored on their own (k_eval_label_scores), sorted per row on the host
-  // by the ranking order, and one sweep over the items (k_eval_count, rows in
-  // chunks, items in slices as in recommend) counts the candidates that fall
-  // between consecutive labels; the prefix sums are the ranks.
+  // ocffm_problem_label_ranks): the rows' layout, then the driver's
+  // label_ranks.
   void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
                    uint32_t *ncand) override {
     need_init();
@@ -1205,120 +1108,19 @@ template <typename real> class Problem final : public ProblemBase {
     if (rows == 0) return;
     sync_owned();
     sync();
-    const auto th0 = std::chrono::steady_clock::now();
+    rank_t0_ = std::chrono::steady_clock::now();
     RecRows L;
     rec_layout(L, X, 0, rows, seen);
-    const uint64_t npop = std::min<uint64_t>(npop_, n_);
-    // each row's distinct candidate labels; every label's place among them
-    const uint64_t ny = X.yptr[rows];
-    std::vector<int64_t> kptr(rows + 1, 0);
-    std::vector<uint32_t> krow, kitem;
-    std::vector<int64_t> where(ny, -1);  // label entry -> its kept label (-1: not a candidate)
-    {
-      std::vector<std::pair<uint32_t, uint64_t>> tmp;
-      for (uint64_t i = 0; i < rows; i++) {
-        const uint64_t lim = L.cold[i] ? npop : n_;
-        const uint32_t *sb = L.lcol.data() + L.lptr[i], *se = L.lcol.data() + L.lptr[i + 1];
-        if (ncand) ncand[i] = (uint32_t)(lim - (uint64_t)(std::lower_bound(sb, se, (uint32_t)lim) - sb));
-        tmp.clear();
-        for (uint64_t p = X.yptr[i]; p < X.yptr[i + 1]; p++) {
-          const uint64_t j = X.ycol[p];
-          if (j < lim && !std::binary_search(sb, se, (uint32_t)j)) tmp.push_back({(uint32_t)j, p});
-        }
-        std::sort(tmp.begin(), tmp.end());
-        for (size_t t = 0; t < tmp.size(); t++) {
-          if (t == 0 || tmp[t].first != tmp[t - 1].first) {
-            krow.push_back((uint32_t)i);
-            kitem.push_back(tmp[t].first);
-          }
-          where[tmp[t].second] = (int64_t)kitem.size() - 1;
-        }
-        kptr[i + 1] = (int64_t)kitem.size();
-      }
-    }
-    const uint64_t nk = kitem.size();
-    for (uint64_t p = 0; p < ny; p++) {
-      ranks[p] = OCFFM_RANK_NONE;
-      if (scores) scores[p] = -std::numeric_limits<double>::infinity();
-    }
-    if (nk == 0) {
-      counters["eval_setup_us"] =
-          (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
-      return;
-    }
-    DevBuf<uint32_t> dcnt;
-    DevBuf<int64_t> dkptr;
-    dkptr.upload(kptr);
-    dcnt.alloc(nk);
-    const RecPlan plan = rec_plan(rows, [](auto K) { return k_eval_count<real, decltype(K)::value>; });
-    const uint64_t chunk = plan.chunk;
-    sync();
-    counters["eval_setup_us"] =
-        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
-    const double depth = (double)C_ * kp_;
-    // the labels' own scores
-    const std::vector<double> kv = score_pairs(L, krow, kitem, "evaluate");
-    // each row's labels in ranking order
-    std::vector<uint32_t> ord(nk);
-    for (uint64_t e = 0; e < nk; e++) ord[e] = (uint32_t)e;
-    for (uint64_t i = 0; i < rows; i++)
-      std::sort(ord.begin() + kptr[i], ord.begin() + kptr[i + 1], [&](uint32_t x, uint32_t y) {
-        return kv[x] > kv[y] || (kv[x] == kv[y] && kitem[x] < kitem[y]);
-      });
-    std::vector<double> sv(nk);
-    std::vector<uint32_t> sj(nk);
-    for (uint64_t e = 0; e < nk; e++) {
-      sv[e] = kv[ord[e]];
-      sj[e] = kitem[ord[e]];
-    }
-    DevBuf<double> dsv;
-    DevBuf<uint32_t> dsj;
-    dsv.upload(sv);
-    dsj.upload(sj);
-    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
-      const uint64_t cr = std::min(chunk, rows - c0);
-      if (kptr[c0 + cr] == kptr[c0]) continue;  // no label in these rows
-      EvalArgs<real> g{};
-      rec_sweep_args(g, L, c0, cr, plan, seen != nullptr);
-      g.kptr = dkptr.p + c0;
-      g.kv = dsv.p;
-      g.kj = dsj.p;
-      g.cnt = dcnt.p;
-      const double bytes = ((double)cr + (double)n_) * depth * sizeof(real) + (double)n_ * sizeof(real) +
-                           (double)(kptr[c0 + cr] - kptr[c0]) * (sizeof(double) + 2 * sizeof(uint32_t));
-      prof_launch("evaluate", bytes, [&] {
-        with_kp(kp_, [&](auto K) {
-          constexpr int KP = decltype(K)::value;
-          launch(k_eval_count<real, KP>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
-        });
-      }, 2.0 * (double)cr * (double)n_ * depth);
-    }
-    std::vector<uint32_t> cnt(nk);
-    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-    sync();
-    flush_prof();
-    // ranks: the prefix sums of each row's counters, back in label order
-    std::vector<uint32_t> krank(nk);
-    for (uint64_t i = 0; i < rows; i++) {
-      uint32_t run = 0;
-      for (int64_t e = kptr[i]; e < kptr[i + 1]; e++) {
-        run += cnt[e];
-        krank[ord[e]] = run;
-      }
-    }
-    for (uint64_t p = 0; p < ny; p++)
-      if (where[p] >= 0) {
-        ranks[p] = krank[where[p]];
-        if (scores) scores[p] = kv[where[p]];
-      }
+    const RankModel<real> m = rank_model();
+    Rank{*this, m}.label_ranks(L, X, seen != nullptr, ranks, scores, ncand, "eval_setup_us");
   }
 
   // ---------------------------------------------------- recommendation
   // Top-N items of rows [row0, row0 + rows) of X (ocffm.h
   // ocffm_problem_recommend).  The rows' user-side layout is built as a test
   // file's is (build_fields with the train Ds) and projected through utx;
-  // the item side is the resident Q_ / V_.bias.  The rows are scored in
-  // chunks: scratch is chunk x slices x topn partial entries, never rows x n.
+  // the item side is the resident Q_ / V_.bias; the driver's recommend does
+  // the rest.
   void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
                  double *scores) override {
     need_init();
@@ -1327,42 +1129,12 @@ template <typename real> class Problem final : public ProblemBase {
     if (rows == 0) return;
     sync_owned();
     sync();
-    const auto th0 = std::chrono::steady_clock::now();
+    rank_t0_ = std::chrono::steady_clock::now();
     const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
     RecRows L;
     rec_layout(L, X, row0, rows, excl ? &X : nullptr);
-    const RecPlan plan = rec_plan(rows, [](auto K) { return k_rec_topn<real, decltype(K)::value>; });
-    const uint64_t chunk = plan.chunk, S = plan.S;
-    DevBuf<double> part_v, out_v;
-    DevBuf<uint32_t> part_j, out_j;
-    part_v.alloc(chunk * S * topn, false);
-    part_j.alloc(chunk * S * topn, false);
-    out_v.alloc(chunk * topn, false);
-    out_j.alloc(chunk * topn, false);
-    sync();
-    counters["rec_setup_us"] =
-        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
-    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
-      const uint64_t cr = std::min(chunk, rows - c0);
-      RecArgs<real> g{};
-      rec_sweep_args(g, L, c0, cr, plan, excl);
-      g.topn = (int)topn;
-      g.part_v = part_v.p;
-      g.part_j = part_j.p;
-      const double depth = (double)C_ * kp_;
-      const double bytes = ((double)cr + (double)n_) * depth * sizeof(real) + (double)n_ * sizeof(real) +
-                           (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
-      prof_launch("recommend", bytes, [&] {
-        with_kp(kp_, [&](auto K) {
-          constexpr int KP = decltype(K)::value;
-          launch(k_rec_topn<real, KP>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
-        });
-        launch(k_rec_merge, (unsigned)cr, BLOCK, 0, cr, (int)S, (int)topn, (const double *)part_v.p,
-               (const uint32_t *)part_j.p, out_j.p, out_v.p);
-      }, 2.0 * (double)cr * (double)n_ * depth);
-      rec_copy_back(c0, cr, topn, out_j, out_v, items, scores);
-    }
-    flush_prof();
+    const RankModel<real> m = rank_model();
+    Rank{*this, m}.recommend(L, rows, topn, excl, items, scores, "rec_setup_us");
   }
 
   // ------------------------------------------------ scores of given pairs
@@ -1378,7 +1150,7 @@ template <typename real> class Problem final : public ProblemBase {
     if (npairs == 0) return;
     sync_owned();
     sync();
-    const auto th0 = std::chrono::steady_clock::now();
+    rank_t0_ = std::chrono::steady_clock::now();
     RecRows L;
     rec_layout(L, X, 0, X.m, nullptr);
     const uint64_t npop = std::min<uint64_t>(npop_, n_);
@@ -1392,10 +1164,10 @@ template <typename real> class Problem final : public ProblemBase {
       where.push_back(e);
     }
     sync();
-    counters["rec_setup_us"] =
-        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
+    rank_setup_done("rec_setup_us");
     if (kitem.empty()) return;
-    const std::vector<double> kv = score_pairs(L, krow, kitem, "rerank");
+    const RankModel<real> m = rank_model();
+    const std::vector<double> kv = Rank{*this, m}.score_pairs(L, krow, kitem, "rerank");
     flush_prof();
     for (size_t t = 0; t < kv.size(); t++) out[where[t]] = kv[t];
   }
@@ -1428,14 +1200,16 @@ template <typename real> class Problem final : public ProblemBase {
     if (rows == 0) return;
     sync_owned();
     sync();
-    const auto th0 = std::chrono::steady_clock::now();
+    rank_t0_ = std::chrono::steady_clock::now();
     const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
     RecRows L;
     rec_layout(L, X, row0, rows, excl ? &X : nullptr);
+    const RankModel<real> m = rank_model();
+    Rank drv{*this, m};
     // work items: row-major, a row's segments in list order
     uint64_t seg = rec_seg_;
     if (!seg) {
-      const unsigned slots = rec_resident([](auto K) { return k_rerank<real, decltype(K)::value>; });
+      const unsigned slots = drv.resident([](auto K) { return k_rerank<real, decltype(K)::value>; });
       seg = cptr[rows] / ((uint64_t)slots * (BLOCK / 64)) + 1;
       seg = (std::clamp(seg, REC_SEG_MIN, REC_SEG_MAX) + 15) / 16 * 16;
     }
@@ -1450,7 +1224,7 @@ template <typename real> class Problem final : public ProblemBase {
       }
       wptr[i + 1] = (int64_t)wrow.size();
     }
-    const uint64_t chunk = rec_chunk(rows);
+    const uint64_t chunk = drv.chunk(rows);
     uint64_t maxw = 0, maxc = 0;
     for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
       const uint64_t c1 = std::min(rows, c0 + chunk);
@@ -1476,8 +1250,7 @@ template <typename real> class Problem final : public ProblemBase {
     out_v.alloc(chunk * topn, false);
     out_j.alloc(chunk * topn, false);
     sync();
-    counters["rec_setup_us"] =
-        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
+    rank_setup_done("rec_setup_us");
     for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
       const uint64_t cr = std::min(chunk, rows - c0);
       const uint64_t nc = cptr[c0 + cr] - cptr[c0];
@@ -1525,7 +1298,7 @@ template <typename real> class Problem final : public ProblemBase {
         launch(k_rerank_merge, (unsigned)((cr + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, cr, c0, g.w0, (int)topn,
                (const int64_t *)dwptr.p, (const double *)part_v.p, (const uint32_t *)part_j.p, out_j.p, out_v.p);
       }, 2.0 * (double)nc * depth);
-      rec_copy_back(c0, cr, topn, out_j, out_v, items, scores);
+      drv.copy_back(c0, cr, topn, out_j, out_v, items, scores);
     }
     flush_prof();
   }

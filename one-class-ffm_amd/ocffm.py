@@ -93,6 +93,7 @@ EXPORTS = [
     "ocffm_sgd_param_default", "ocffm_sgd_create", "ocffm_sgd_create_dist", "ocffm_sgd_create_dist_host", "ocffm_sgd_epoch",
     "ocffm_sgd_average", "ocffm_sgd_phi", "ocffm_sgd_get", "ocffm_sgd_set_w", "ocffm_sgd_get_info",
     "ocffm_sgd_sync", "ocffm_sgd_destroy",
+    "ocffm_sgd_recommend", "ocffm_sgd_label_ranks", "ocffm_sgd_evaluate", "ocffm_sgd_counter",
 ]
 
 _lib = None
@@ -166,6 +167,10 @@ def lib():
     L.ocffm_sgd_get_info.argtypes = [vp, vp]
     L.ocffm_sgd_sync.argtypes = [vp]
     L.ocffm_sgd_destroy.argtypes = [vp]
+    L.ocffm_sgd_recommend.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp]
+    L.ocffm_sgd_label_ranks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ocffm_sgd_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_sgd_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     L.ocffm_sgd_destroy.restype = None
     _lib = L
     return L
@@ -366,6 +371,52 @@ class SgdTrainer:
 
     def sync(self) -> None:
         _check(lib().ocffm_sgd_sync(self.h))
+
+    def recommend(self, X: "ImpData", topn: int = 10, exclude_labels: bool = False, row0: int = 0,
+                  rows: Optional[int] = None):
+        """Top-``topn`` items of rows [row0, row0 + rows) of ``X`` (default: to its
+        end) under the current W (include/ocffm.h ocffm_sgd_recommend):
+        ``(items uint32 [rows, topn], scores float64 [rows, topn])``, score
+        descending, equal scores by ascending item; unfilled slots hold
+        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels."""
+        if rows is None:
+            rows = max(0, int(X.info["m"]) - row0)
+        shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
+        items = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        flags = REC_EXCLUDE_LABELS if exclude_labels else 0
+        _check(lib().ocffm_sgd_recommend(self.h, X.h, row0, rows, topn, flags, items.ctypes.data_as(C.c_void_p),
+                                         scores.ctypes.data_as(C.c_void_p)))
+        return items, scores
+
+    def label_ranks(self, X: "ImpData", seen: Optional["ImpData"] = None):
+        """Exact rank of every label of ``X`` among its row's candidates
+        (include/ocffm.h ocffm_sgd_label_ranks): ``(ranks uint32 [nnz_y], scores
+        float64 [nnz_y], ncand uint32 [m])`` in ``X.labels()`` order.  ``seen``
+        (same row count) removes its rows' labels from the candidates; a label
+        that is no candidate has ``RANK_NONE`` / ``-inf``."""
+        i = X.info
+        ranks = np.full(max(1, i["nnz_y"]), RANK_NONE, dtype=np.uint32)
+        scores = np.full(max(1, i["nnz_y"]), -np.inf, dtype=np.float64)
+        ncand = np.zeros(max(1, i["m"]), dtype=np.uint32)
+        _check(lib().ocffm_sgd_label_ranks(self.h, X.h, None if seen is None else seen.h, _ptr(ranks), _ptr(scores),
+                                           _ptr(ncand)))
+        return ranks[: i["nnz_y"]], scores[: i["nnz_y"]], ncand[: i["m"]]
+
+    def evaluate(self, X: "ImpData", cuts=(5, 10, 20, 40, 80), seen: Optional["ImpData"] = None) -> dict:
+        """Ranking metrics of the current W on the labelled rows ``X``
+        (include/ocffm.h ocffm_sgd_evaluate): the dict of
+        ``ImpProblem.evaluate``."""
+        c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+        e = _Eval()
+        _check(lib().ocffm_sgd_evaluate(self.h, X.h, None if seen is None else seen.h, _ptr(c), c.size, C.byref(e)))
+        return e.as_dict()
+
+    def counter(self, name: str) -> int:
+        """Serving counter (include/ocffm.h ocffm_sgd_counter)."""
+        v = C.c_int64(0)
+        _check(lib().ocffm_sgd_counter(self.h, name.encode(), C.byref(v)))
+        return v.value
 
 
 def comm_id() -> bytes:
