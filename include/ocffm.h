@@ -408,8 +408,15 @@ int ocffm_problem_alg_bytes(ocffm_problem *p, double *bytes);
  * halves), "cgp_side_launches" (the latter), "cgp_side_full" (side halves
  * whose gradient and update ran inside the launch), "cgp_recovered"
  * (launches whose grid gave up on its barrier and whose solve was finished
- * per step), "cgp_refused" (cooperative launches the runtime refused).
- * An unknown name reads 0. */
+ * per step), "cgp_refused" (cooperative launches the runtime refused),
+ * "cgp_side_sm1" / "_sm2" / "_sm4" (id-like side launches by rows per
+ * subgroup) and "cgp_side_res_sm1" / "_sm2" / "_sm4" (the resident grid last
+ * found for that variant, in blocks), "xfuse_steps" (fused id-field cross
+ * steps) and "xfuse_strided" (those on fewer blocks than their rows fill),
+ * "ccg_halves" (cross halves solved on per-column Grams), "hot_halves"
+ * (cross halves whose steps read hot rows' Grams), "capped_launches"
+ * (launches whose grid a residency or *_BLOCKS cap cut below its work, so
+ * that its blocks loop).  An unknown name reads 0. */
 int ocffm_problem_counter(ocffm_problem *p, const char *name, int64_t *value);
 int ocffm_problem_sync(ocffm_problem *p);
 /* Digests (FNV-1a over the bytes) of every array of the device data layout

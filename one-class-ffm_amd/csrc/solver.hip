@@ -349,6 +349,10 @@ struct ProblemBase {
   std::string prof_filter;
   double alg_bytes = 0;
   std::map<std::string, int64_t> counters;  // diagnostics (ocffm_problem_counter)
+  // per-launch diagnostics, plain words (read under their names by ocffm_problem_counter):
+  // launches whose grid a resident() or *_blocks_ cap cut below its work, k_hv_cross_id
+  // launches, and those of them that stride
+  int64_t n_capped = 0, n_xfuse = 0, n_xfuse_strided = 0;
 };
 
 struct Comm {
@@ -461,6 +465,10 @@ template <typename real> class Problem final : public ProblemBase {
       HIPCHK(hipGetDevice(&dev));
       HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
       ncu_ = (unsigned)std::max(1, ncu);
+      // OCFFM_NCU=n (tests): plan as on a device of n CUs, never more than
+      // the real count (the persistent kernels' barriers need co-residency):
+      // every resident() cap and k_cg_cgram's grid bound shrink at once
+      if (const char *e = std::getenv("OCFFM_NCU")) ncu_ = (unsigned)std::clamp(std::atoi(e), 1, (int)ncu_);
     }
     cgp_gen_buf_.alloc(1);
     cgp_abort_.alloc(1);
@@ -1884,8 +1892,15 @@ template <typename real> class Problem final : public ProblemBase {
   // gradient, update and column-Gram step passes; no LDS)
   bool misc_fill_ = !std::getenv("OCFFM_MISC_FILL") || std::atoi(std::getenv("OCFFM_MISC_FILL")) != 0;
   template <typename... KArgs> unsigned mfill(void (*k)(KArgs...), unsigned grid) {
-    return misc_fill_ ? std::min(grid, resident(k, 0)) : grid;
+    return misc_fill_ ? capped(grid, std::min(grid, resident(k, 0))) : grid;
   }
+  // `got` blocks for `want` blocks' worth of work: counts the launches whose
+  // blocks loop ("capped_launches")
+  unsigned capped(uint64_t want, uint64_t got) {
+    if (got < want) n_capped++;
+    return (unsigned)got;
+  }
+  static uint64_t blocks_of(uint64_t items, uint64_t per_block) { return (items + per_block - 1) / per_block; }
   template <typename... KArgs, typename... A>
   void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t smem, A... a) {
     static_assert(sizeof...(KArgs) == sizeof...(A), "kernel argument count");
@@ -2043,6 +2058,7 @@ template <typename real> class Problem final : public ProblemBase {
     const unsigned gy = (unsigned)((L + 1 + TPB - 1) / TPB);  // L table slots + the sums slot
     const uint64_t nout = (uint64_t)L * 4096 + 129;
     uint64_t nbx = std::max<uint64_t>(1, std::min<uint64_t>((Rp + 63) / 64, std::max<uint64_t>(1, gram64_blocks_ / gy)));
+    capped((Rp + 63) / 64, nbx);
     const uint64_t rpb = ((Rp + nbx - 1) / nbx + 15) / 16 * 16;  // whole rounds of row pairs
     nbx = std::max<uint64_t>(1, (Rp + rpb - 1) / rpb);
     if (gpart64_.n < nbx * nout) gpart64_.alloc(nbx * nout, false);
@@ -2068,6 +2084,7 @@ template <typename real> class Problem final : public ProblemBase {
     const unsigned gy = (unsigned)((L + 1 + TPB - 1) / TPB);
     const uint64_t nout = (uint64_t)L * 1024 + 65;
     uint64_t nbx = std::max<uint64_t>(1, std::min<uint64_t>((Rp + 63) / 64, std::max<uint64_t>(1, gram64_blocks_ / gy)));
+    capped((Rp + 63) / 64, nbx);
     const uint64_t rpb = ((Rp + nbx - 1) / nbx + 31) / 32 * 32;  // whole rounds of 2 x 4 x 4 rows
     nbx = std::max<uint64_t>(1, (Rp + rpb - 1) / rpb);
     if (gpartd_.n < nbx * nout) gpartd_.alloc(nbx * nout, false);
@@ -2102,6 +2119,7 @@ template <typename real> class Problem final : public ProblemBase {
       const double abytes = (double)Rp * ((L + (B ? 1 : 0)) * kp_ + (wv ? 1 : 0)) * sizeof(real);
       if (mg) {  // fp32, KP = 32: the Grams on MFMA (kernels.hpp k_gram_mfma32)
         nbx = std::max<uint64_t>(1, std::min<uint64_t>((Rp + 127) / 128, gram_blocks_));
+        capped((Rp + 127) / 128, nbx);
         nbx = std::min<uint64_t>(nbx, std::max<uint64_t>(1, part_.n / nout));
         const uint64_t rpbm = (Rp + nbx - 1) / nbx;
         prof_launch("aggregates", abytes, [&] {
@@ -2300,7 +2318,7 @@ template <typename real> class Problem final : public ProblemBase {
           if constexpr (std::is_same<real, float>::value && (KP == 32 || KP == 64)) {
             const uint64_t nb = (own.R + RowsT<KP>::ROWS - 1) / RowsT<KP>::ROWS;
             prof_launch("rows_T", (double)C_ * own.R * KP * rs + (double)own.R * KP * rs + (double)C_ * KP * KP * rs, [&] {
-              launch(k_rows_T<KP>, (unsigned)std::min<uint64_t>(nb, tpre_blocks_), TBLOCK, 0, (uint64_t)own.R, (int)C_,
+              launch(k_rows_T<KP>, capped(nb, std::min<uint64_t>(nb, tpre_blocks_)), TBLOCK, 0, (uint64_t)own.R, (int)C_,
                      (const float *const *)(tabs_.p + (h.user ? 0 : C_)), (const float *)M_.p, (float *)Tpre_.p);
             }, 2.0 * own.R * C_ * KP * KP);
           }
@@ -2317,6 +2335,7 @@ template <typename real> class Problem final : public ProblemBase {
             const size_t gsm = TP ? 0 : (ML ? msz + (TM ? TMma<real, KP>::tile_bytes() : 0) : 0);
             unsigned grid = grid_for(own.nseg, 4 * Gm::NSG, gd_blocks_);
             if (gd_fill_) grid = std::min(grid, resident(k_gd_cross_seg<real, KP, ML, BM, TP>, gsm));
+            capped(blocks_of(own.nseg, 4 * Gm::NSG), grid);
             launch(k_gd_cross_seg<real, KP, ML, BM, TP>, grid, BLOCK, gsm, own.nseg, own.segs.p, own.ycol.p, own.yt.p, h.Q1, (int)C_,
                 (const real *const *)(tabs_.p + (h.user ? 0 : C_)), M_.p, sums_.p, own.bias.p, h.partner->bias.p, w_,
                 r_, h_.p, (uint64_t)h.partner->R, cur, drow, dxs, (const uint32_t *)own.perm.p,
@@ -2657,6 +2676,7 @@ template <typename real> class Problem final : public ProblemBase {
   void hot_grams(const HalfCtx &h, bool force = false) {
     if (!(force ? h.own->nhot > 0 && hotG_.p : hot(h))) return;
     DevSide<real> &own = *h.own;
+    counters["hot_halves"]++;  // this half's steps read hot rows' Grams (hot(), or k_hv_cross_id's hot rows)
     const double kk = (double)kp_ * kp_, rs = sizeof(real);
     GramBuild b;
     b.name = "hot_gram";
@@ -3167,7 +3187,9 @@ template <typename real> class Problem final : public ProblemBase {
       const unsigned grid0 = (unsigned)std::min<uint64_t>((njw + 3) / 4, feat_blocks_);  // grid-stride: fewer tickets
       // at most one resident wave of blocks (OCFFM_FEAT_FILL): fp64's
       // register count holds fewer blocks per CU than the fp32 cap assumes
-      auto fill = [&](auto k, size_t sm) { return feat_fill_ ? std::min(grid0, resident(k, sm)) : grid0; };
+      auto fill = [&](auto k, size_t sm) {
+        return capped((njw + 3) / 4, feat_fill_ ? std::min(grid0, resident(k, sm)) : grid0);
+      };
       Fin<real> fin = make_fin(h, it);
       fin.hdots = seg ? F.shdots.p : F.hdots.p;
       fin.nhd = (uint32_t)(seg ? F.snslot : F.nslot);
@@ -3423,7 +3445,8 @@ template <typename real> class Problem final : public ProblemBase {
         prof_launch("hs_cross_io", (double)io.nseg * (24 + 8 + rs) + (double)io.nseg * KP * rs * 2, [&] {
           auto go = [&](auto ml) {
             constexpr bool ML = decltype(ml)::value;
-            launch(k_hs_cross_seg<real, KP, ML>, grid_for(io.nseg, 4 * Gm::NSG, hs_blocks_), BLOCK, lds ? qsz : 0,
+            launch(k_hs_cross_seg<real, KP, ML>,
+                   capped(blocks_of(io.nseg, 4 * Gm::NSG), grid_for(io.nseg, 4 * Gm::NSG, hs_blocks_)), BLOCK, lds ? qsz : 0,
                    io.nseg, io.segs.p, F.xptr.p, F.xidx.p, F.xval.p, Vd_.p, io.ycol.p, (const real *)Pg_.p,
                    (uint64_t)comm_.nranks * io_cu_, ct ? (const real *)nullptr : (const real *)qtqg_.p, w_, h_.p,
                    run, Rv_.p, Hv_.p, st_.p, it, io.segd.p, io.segx.p, (const uint32_t *)nullptr,
@@ -3438,7 +3461,7 @@ template <typename real> class Problem final : public ProblemBase {
       } else {
         fin.hdots = io.shdots.p;
         fin.nhd = (uint32_t)io.snslot;
-        const unsigned grid = (unsigned)std::min<uint64_t>((io.snjw + 3) / 4, feat_blocks_);
+        const unsigned grid = capped((io.snjw + 3) / 4, std::min<uint64_t>((io.snjw + 3) / 4, feat_blocks_));
         prof_launch("feat_hv_io", (double)io.scrow.n * (4 + rs) * 2 + (double)io.snjw * Gm::NSG * sizeof(Job), [&] {
           if constexpr ((size_t)KP * KP * sizeof(real) <= COLTAU_LDS) {
             if (ct) {
@@ -3552,11 +3575,18 @@ template <typename real> class Problem final : public ProblemBase {
       auto fits = [&](auto sm) {
         constexpr int SM = decltype(sm)::value;
         const unsigned res = full ? resident(k_cg_side_id<real, KP, SM, true>, 0) : resident(k_cg_side_id<real, KP, SM>, 0);
+        counters[SM == 1 ? "cgp_side_res_sm1" : SM == 2 ? "cgp_side_res_sm2" : "cgp_side_res_sm4"] = res;
         return (R + SM * 4 * Gm::NSG - 1) / (SM * 4 * Gm::NSG) <= res;
       };
       if (fits(std::integral_constant<int, 1>())) smax = 1;
       else if (fits(std::integral_constant<int, 2>())) smax = 2;
       else if (fits(std::integral_constant<int, 4>())) smax = 4;
+      // OCFFM_SIDEP_SM (tests): more rows per subgroup than the rows need,
+      // where the rows fit the resident grid at that variant's own occupancy
+      if (smax && sidep_sm_ > smax) {
+        if (sidep_sm_ == 2 && fits(std::integral_constant<int, 2>())) smax = 2;
+        if (sidep_sm_ == 4 && fits(std::integral_constant<int, 4>())) smax = 4;
+      }
     });
     return smax;
   }
@@ -3580,6 +3610,7 @@ template <typename real> class Problem final : public ProblemBase {
       counters["cgp_launches"]++;
       counters["cgp_side_launches"]++;
       if (full) counters["cgp_side_full"]++;
+      counters[smax == 1 ? "cgp_side_sm1" : smax == 2 ? "cgp_side_sm2" : "cgp_side_sm4"]++;
       const double rs = sizeof(real);
       const double bytes = (double)own.R * KP * rs * 9 + (double)own.R * (4 + rs + 16);
       DevSide<real> &other = h.user ? V_ : U_;
@@ -3702,6 +3733,8 @@ template <typename real> class Problem final : public ProblemBase {
           // one resident wave of blocks in both precisions (~3 rows per
           // subgroup, the next row's descriptor in flight; fp32: 4.99 -> 4.78 ms)
           grid = std::min(grid, resident(k_hv_cross_id<real, KP, GB>, 0));
+          n_xfuse++;
+          if (capped(blocks_of(own.R, 4 * Gm::NSG), grid) < blocks_of(own.R, 4 * Gm::NSG)) n_xfuse_strided++;
           launch(k_hv_cross_id<real, KP, GB>, grid, BLOCK, 0, own.R, F.xidx.p, F.xval.p, (const int64_t *)own.yptr.p,
                  (const uint32_t *)own.ycol.p, h.Q1, (uint64_t)h.partner->R, (const real *)qtq_, w_,
                  hotr ? (const uint32_t *)own.hot_row.p : (const uint32_t *)nullptr, (const real *)hotG_.p, fin);
@@ -3789,6 +3822,7 @@ template <typename real> class Problem final : public ProblemBase {
                 unsigned grid = TT ? grid_for(own.nseg, TauTile<real, KP>::SB, hs_blocks_)
                                    : grid_for(own.nseg, 4 * Gm::NSG, hs_blocks_);
                 if (row_fill_) grid = std::min(grid, resident(k_hs_cross_seg<real, KP, ML, PW, TT>, sm));
+                capped(blocks_of(own.nseg, TT ? TauTile<real, KP>::SB : 4 * Gm::NSG), grid);
                 launch(k_hs_cross_seg<real, KP, ML, PW, TT>, grid, BLOCK, sm,
                        own.nseg, own.segs.p, F.xptr.p, F.xidx.p, F.xval.p, Vd_.p, own.ycol.p, h.Q1,
                        (uint64_t)h.partner->R, coltau(h) ? (const real *)nullptr : (const real *)qtq_, w_, h_.p, run,
@@ -3819,6 +3853,7 @@ template <typename real> class Problem final : public ProblemBase {
             constexpr bool FZ = decltype(fz)::value, SC = decltype(sc)::value;
             unsigned grid = grid_for(own.R, 4 * Gm::NSG, FZ ? 2048u : 4096u);
             if (side_fill_) grid = std::min(grid, resident(k_hs_side_row<real, KP, FZ, SC>, 0));
+            capped(blocks_of(own.R, 4 * Gm::NSG), grid);
             launch(k_hs_side_row<real, KP, FZ, SC>, grid, BLOCK, 0,
                 own.R, F.xptr.p, F.xidx.p, F.xval.p, Vd_.p, hess_cnt(h), h.Q1, w_, n1, h_.p, run, Rv_.p, Hv_.p, st_.p, it,
                 F.one, fin);
@@ -3889,6 +3924,7 @@ template <typename real> class Problem final : public ProblemBase {
     const int last = key < pred_.size() ? pred_[key] : 0;
     ccg_now_ = ccg_eligible(h) && (ccg_mode_ == 2 || last >= 3);
     hot_now_ = last >= hot_steps_;
+    if (ccg_now_) counters["ccg_halves"]++;
     int it0 = 1;
     const int sfull = sidep_smax(h, true);
     if (sfull) {
@@ -4233,6 +4269,7 @@ template <typename real> class Problem final : public ProblemBase {
   bool cgp_xcd_ = !std::getenv("OCFFM_CGP_XCD") || std::atoi(std::getenv("OCFFM_CGP_XCD")) != 0;
   // OCFFM_SIDEP=0: id-like side halves' CG per step (k_hs_side_row FUSE) instead of k_cg_side_id
   bool sidep_on_ = !std::getenv("OCFFM_SIDEP") || std::atoi(std::getenv("OCFFM_SIDEP")) != 0;
+  int sidep_sm_ = std::getenv("OCFFM_SIDEP_SM") ? std::atoi(std::getenv("OCFFM_SIDEP_SM")) : 0;  // 2 | 4: at least that SM
   // OCFFM_SIDE_FULL=0: id-like side halves run gradient and update as their own launches around k_cg_side_id
   bool sidef_on_ = !std::getenv("OCFFM_SIDE_FULL") || std::atoi(std::getenv("OCFFM_SIDE_FULL")) != 0;
   // OCFFM_XFUSE=0: id-like cross halves' CG steps as k_hs_cross_seg + feature pass instead of k_hv_cross_id
@@ -4694,7 +4731,11 @@ int ocffm_problem_counter(ocffm_problem *prob, const char *name, int64_t *value)
   PROB_CALL({
     if (!name || !value) throw Error(OCFFM_E_ARG, "null argument");
     const auto it = prob->p->counters.find(name);
-    *value = it == prob->p->counters.end() ? 0 : it->second;
+    const std::string nm(name);
+    *value = nm == "capped_launches" ? prob->p->n_capped
+             : nm == "xfuse_steps"   ? prob->p->n_xfuse
+             : nm == "xfuse_strided" ? prob->p->n_xfuse_strided
+             : it == prob->p->counters.end() ? 0 : it->second;
   });
 }
 int ocffm_problem_sync(ocffm_problem *prob) { PROB_CALL(prob->p->sync()); }

@@ -334,6 +334,46 @@ def kkbox_small(seed: int = 11) -> Dataset:
     return kkbox(seed=seed, m=2000, n=3000, mean=30.0, name="kkbox_small")
 
 
+def permute_ids(ds: Dataset, seed: int, lo: float = 0.75, span: float = 0.5, item_order: bool = False) -> Dataset:
+    """The id fields (field 0 of both sides) of a kkbox-shaped set in shuffled
+    order with real values: row i's id node becomes (0, perm[i], x_i), x_i in
+    [lo, lo + span) rounded to three decimals.  The fields stay id-like (one
+    node per row, every feature in exactly one row) but row != column and
+    x != 1 != x^2, as in a real input, whose listener and song ids are in file
+    order only by accident.  Train and test rows share the listener
+    permutation; every other node keeps value 1 (a wider range, or real
+    values on every node, puts the reference's own CG stop criterion on
+    near-ties: DESIGN §Parity).  item_order: the item ids keep their order
+    (item j -> column j, which the item-owned CG steps of several ranks
+    require) and only take the real values."""
+    rng = np.random.default_rng(seed + 1000)
+    pu = rng.permutation(ds.train.m)
+    pv = rng.permutation(ds.item.m)
+    if item_order:
+        pv = np.arange(ds.item.m)
+
+    def shuffled(rows, perm):
+        if rows is None:
+            return None
+        sel = rows.fid == 0
+        idx, val = rows.idx.copy(), rows.val.copy()
+        idx[sel] = perm[rows.idx[sel].astype(np.int64)].astype(np.uint64)
+        val[sel] = np.round(lo + span * rng.random(int(sel.sum())), 3)
+        return Rows(rows.xptr, rows.fid, idx, val, rows.yptr, rows.ycol)
+
+    train = shuffled(ds.train, pu)
+    item = shuffled(ds.item, pv)
+    test = shuffled(ds.test, pu)
+    return Dataset(ds.name, train, item, test, ds.k, dict(ds.params))
+
+
+def kkbox_perm() -> Dataset:
+    """kkbox shape at 1,500 x 2,500 (neither a multiple of a block's rows)
+    with permuted, real-valued id fields: the parity tests' net under the
+    kernels specialised for id-like fields (tests/test_idfield_paths.py)."""
+    return permute_ids(kkbox(seed=21, m=1500, n=2500, mean=30.0, name="kkbox_perm"), 21)
+
+
 def kkbox_s(seed: int = 7) -> Dataset:
     """kkbox-shape-S: m=30,000, n=20,000, mean 30."""
     return kkbox(seed=seed, m=30000, n=20000, mean=30.0, name="kkbox_s")

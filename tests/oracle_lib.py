@@ -105,7 +105,12 @@ def block_index(f1, f2, f):
 
 
 class Oracle:
-    """The restated reference problem (ImpProblem, ffm.h:82-151)."""
+    """The restated reference problem (ImpProblem, ffm.h:82-151).
+
+    `threads` becomes the process's OpenMP thread count (omp_set_num_threads
+    at create), while an oracle sizes its per-thread buffers by its own
+    count: do not call into an oracle while one created later with MORE
+    threads has set the count (heap overflow); free the wider one first."""
 
     def __init__(self, ds, k=None, omega=None, lam=None, r=None, t=None, threads=1, self_side=True,
                  freq=False, with_test=True, seed=1):

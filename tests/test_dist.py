@@ -179,6 +179,18 @@ def _dist_dataset(name):
         # (ceil(37/N): 13/13/11, 10/10/10/7: the all-gather slots r >= 2 hold
         # short chunks); the listener-id field is owned
         return synth.kkbox(seed=9, m=301, n=37, mean=8.0, name="uneven")
+    if name == "perm_uneven":
+        # the same with shuffled, real-valued id fields: each rank's owned
+        # listener-id columns lie scattered over D instead of in one range, and
+        # the owned song columns do not line up with the item-row chunks
+        # (the item-owned CG steps need item j -> column j, solver.hip io_setup:
+        # with shuffled song ids their halves take the all-reduce path)
+        return synth.permute_ids(synth.kkbox(seed=9, m=301, n=37, mean=8.0, name="perm_uneven"), 9)
+    if name == "perm_users_uneven":
+        # shuffled listener ids, real values on both id fields, the song ids in
+        # item order: the item-owned steps run, over scattered owned listener columns
+        return synth.permute_ids(synth.kkbox(seed=9, m=301, n=37, mean=8.0, name="perm_users_uneven"), 9,
+                                 item_order=True)
     if name == "outbrain":
         # BASELINE configs[3]'s data-parallel workload at test size (SURVEY
         # §8d): fu = 2, fv = 2, k = 64, ~1 positive per row
@@ -229,7 +241,8 @@ def _gpu_worker(rank, port, out_dir, world, name="tiny"):
                                       ("lowcard", {"OCFFM_CCG": "2", "OCFFM_HOT": "2"}),
                                       ("owned", {"OCFFM_ITEM_OWNED": "0"}),
                                       ("owned", {"OCFFM_ITEM_OWNED": "0", "OCFFM_CCG": "2"}),
-                                      ("owned", {"OCFFM_EXACT_R2": "1"}), ("one_item", {"OCFFM_ITEM_OWNED": "2"})])
+                                      ("owned", {"OCFFM_EXACT_R2": "1"}), ("one_item", {"OCFFM_ITEM_OWNED": "2"}),
+                                      ("perm_uneven", {}), ("perm_users_uneven", {})])
 def test_two_ranks_match_one_rank_on_gpu(name, env, monkeypatch):
     import ocffm
     for k, v in env.items():  # inherited by the spawned ranks
@@ -249,9 +262,9 @@ def test_two_ranks_match_one_rank_on_gpu(name, env, monkeypatch):
         # the owned-field path ran on the listener-id halves, and the song-id
         # item halves' CG steps ran item-owned (the default on several ranks)
         # unless OCFFM_ITEM_OWNED=0
-        if name == "owned":
+        if name in ("owned", "perm_uneven", "perm_users_uneven"):
             assert int(r0["steps"]) > 0
-            io_on = env.get("OCFFM_ITEM_OWNED", "1") != "0"
+            io_on = env.get("OCFFM_ITEM_OWNED", "1") != "0" and name != "perm_uneven"
             assert (int(r0["io"]) > 0) == io_on and (int(r1["io"]) > 0) == io_on
         if name == "one_item":  # rank 1 owns no item: it only joins the collectives
             assert int(r0["io"]) > 0 and int(r1["io"]) == 0
@@ -270,7 +283,9 @@ def test_two_ranks_match_one_rank_on_gpu(name, env, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,name,env", [(3, "uneven", {}), (4, "uneven", {}), (4, "uneven", {"OCFFM_CCG": "2"}),
                                             (3, "uneven", {"OCFFM_ITEM_OWNED": "0"}),
-                                            (3, "one_item", {"OCFFM_ITEM_OWNED": "2"}), (4, "outbrain", {})])
+                                            (3, "one_item", {"OCFFM_ITEM_OWNED": "2"}), (4, "outbrain", {}),
+                                            (3, "perm_uneven", {}), (3, "perm_uneven", {"OCFFM_ITEM_OWNED": "0"}),
+                                            (3, "perm_users_uneven", {})])
 def test_n_ranks_match_one_rank_on_gpu(world, name, env, monkeypatch):
     """3 and 4 ranks on one device (all-reduces through the host hook):
     uneven user shards, owned listener-id fields, item-owned CG steps whose
@@ -291,8 +306,9 @@ def test_n_ranks_match_one_rank_on_gpu(world, name, env, monkeypatch):
             g.one_epoch()
         met = g.validate()
         nb = g.n_blocks()
-        if name == "uneven":
-            io_on = env.get("OCFFM_ITEM_OWNED", "1") != "0"
+        if name in ("uneven", "perm_uneven", "perm_users_uneven"):
+            # (perm_uneven: no item-owned steps on song ids that are not in item order)
+            io_on = env.get("OCFFM_ITEM_OWNED", "1") != "0" and name != "perm_uneven"
             assert all((int(r["io"]) > 0) == io_on for r in rs)
             assert all(int(r["steps"]) > 0 for r in rs)  # owned listener-id halves
         if name == "one_item":

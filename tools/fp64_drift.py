@@ -64,6 +64,15 @@ SETS = {
     "kkbox_full": (lambda: synth.kkbox(test_frac=0.05), dict()),
     # config 2 at its own size (500 k x 50 k, k = 16; test_kdd12_full_size_parity_fp64)
     "kdd12_full": (lambda: synth.kdd12(test_rows=500), dict()),
+    # permuted, real-valued id fields (tests/test_idfield_paths.py; tests/test_dist.py "perm_uneven")
+    "kkbox_perm": (synth.kkbox_perm, dict()),
+    "kkbox_perm_k5": (synth.kkbox_perm, dict(k=5)),
+    "kkbox_perm_k64": (synth.kkbox_perm, dict(k=64)),
+    "kkbox_perm_k128": (synth.kkbox_perm, dict(k=128)),
+    "perm_uneven": (lambda: synth.permute_ids(synth.kkbox(seed=9, m=301, n=37, mean=8.0, name="perm_uneven"), 9),
+                    dict()),
+    "perm_users_uneven": (lambda: synth.permute_ids(synth.kkbox(seed=9, m=301, n=37, mean=8.0,
+                                                                name="perm_users_uneven"), 9, item_order=True), dict()),
 }
 
 
