@@ -202,9 +202,12 @@ __global__ __launch_bounds__(256, OCC) void k_sgd(Args d, int smax) {
       }
     }
     const float phi = xsg_sum<LPR>(acc) * rn;
-    const float ex = expf(-y * phi);
-    const float kappa = -y * ex / (1.0f + ex);
-    if (lane == 0) lsum += log1p((double)ex);
+    // logistic in its saturating form: one exp of -|z|, z = -y phi, so that z past
+    // expf's range gives |kappa| = 1 and loss z, not inf / inf
+    const float z = -y * phi;
+    const float ex = expf(-fabsf(z));
+    const float kappa = -y * (z > 0 ? 1.0f / (1.0f + ex) : ex / (1.0f + ex));
+    if (lane == 0) lsum += (double)fmaxf(z, 0.0f) + log1p((double)ex);
     // slot steps
 #pragma unroll
     for (int t = 0; t < SPG; t++) {

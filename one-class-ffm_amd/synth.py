@@ -379,6 +379,85 @@ def kkbox_s(seed: int = 7) -> Dataset:
     return kkbox(seed=seed, m=30000, n=20000, mean=30.0, name="kkbox_s")
 
 
+def multi_hot(seed: int, fu: int, fv: int, nu: int, nv: int, m: int = 24, n: int = 20,
+              name: str = "multi_hot") -> Dataset:
+    """Hand-built rows for the SGD kernel's wide instances
+    (tests/test_sgd_paths.py): m users over fu fields and n items over fv
+    fields, real values in [0.25, 2].  Row 0 of either side is the widest (nu /
+    nv nodes), user row 1 has one node, user row 2 and item row 1 have none,
+    every other row has 1..nu (1..nv) nodes.  A row's nodes go round the
+    fields (the start moves on from row to row, so every field is used), several
+    per field where the row is wider than the field count; no feature appears
+    twice within one row, and every field's last feature appears.  User 0 has
+    item 0 among its positives (the widest instance), user 1 item 1, user 2
+    items 0 and 1 (a user without nodes meets the widest and the empty item);
+    every user has 1..3 positives."""
+    rng = np.random.default_rng(seed)
+
+    def side(count, nf, wide, widths):
+        per = -(-wide // nf)  # most nodes one row puts into one field
+        d = per + 4           # features per field; the last one is placed below
+        feats, start = [], 0
+        for w in widths:
+            cnt = np.bincount((start + np.arange(w)) % nf, minlength=nf)
+            start += w
+            row = []
+            for f in range(nf):
+                for j in rng.choice(d - 1, size=int(cnt[f]), replace=False):
+                    row.append((f, int(j), float(np.round(rng.uniform(0.25, 2.0), 3))))
+            feats.append(row)
+        rows = _build_rows(feats, None)
+        for f in range(nf):
+            sel = np.flatnonzero(rows.fid == f)
+            if sel.size == 0:
+                raise ValueError(f"field {f} has no node: more rows are needed")
+            rows.idx[sel[-1]] = d - 1  # no other node holds it: still no feature twice in a row
+        return rows
+
+    uw = [nu, 1, 0] + [int(rng.integers(1, nu + 1)) for _ in range(m - 3)]
+    vw = [nv, 0] + [int(rng.integers(1, nv + 1)) for _ in range(n - 2)]
+    train = side(m, fu, nu, uw)
+    item = side(n, fv, nv, vw)
+    labels = [np.sort(rng.choice(n, size=int(rng.integers(1, 4)), replace=False)) for _ in range(m)]
+    labels[0] = np.union1d(labels[0], [0])
+    labels[1] = np.union1d(labels[1], [1])
+    labels[2] = np.array([0, 1])
+    lc = np.fromiter((len(l) for l in labels), dtype=np.uint64, count=m)
+    train.yptr = np.zeros(m + 1, dtype=np.uint64)
+    np.cumsum(lc, out=train.yptr[1:])
+    train.ycol = np.concatenate(labels).astype(np.uint64)
+    return Dataset(name, train, item, None, k=4, params={})
+
+
+def conflict_free(m: int, rich: bool, seed: int = 1, ends: bool = False, name: str = "conflict_free") -> Dataset:
+    """m users and m items, user i with exactly one positive, item perm[i],
+    and no feature shared between two rows: trained without negatives, no two
+    instances of an epoch touch the same row of W, so the result does not
+    depend on the instance order or on which wave ran what
+    (tests/test_sgd_paths.py).  rich: either side has an id field (row i: id i)
+    and a two-node field {2i, 2i + 1} (F = 4, six nodes per instance); else one
+    id node per side (F = 2).  ends (with rich): the users' two-node field
+    comes first, so that an instance's first slot (node 0, field 0) and its last
+    (node 5, field 3) both have a partner and are both in use.  Real values in
+    [0.25, 2]; vectorised."""
+    rng = np.random.default_rng(seed)
+    perm = rng.permutation(m)
+    ids = np.arange(m, dtype=np.uint64)[:, None]
+
+    def side(pair_first):
+        fields = [(ids, np.round(rng.uniform(0.25, 2.0, (m, 1)), 3))]
+        if rich:
+            pair = 2 * ids + np.arange(2, dtype=np.uint64)[None, :]
+            fields.append((pair, np.round(rng.uniform(0.25, 2.0, (m, 2)), 3)))
+        if pair_first:
+            fields.reverse()
+        return [(f, ix, vx) for f, (ix, vx) in enumerate(fields)]
+
+    train = _fast_rows(m, side(rich and ends), np.arange(m + 1), perm)
+    item = _fast_rows(m, side(False))
+    return Dataset(name, train, item, None, k=4, params={})
+
+
 def _two_distinct(rng, m, d):
     a = rng.integers(0, d, size=m)
     b = rng.integers(0, d - 1, size=m)

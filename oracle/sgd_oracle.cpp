@@ -18,8 +18,11 @@
 //   item = coin < prob[idx] ? idx : alias[idx].
 //   nodes = user row nodes ++ item row nodes (global feature ids, fields).
 //   phi = rn sum_{a<b} <W[j_a][f_b], W[j_b][f_a]> x_a x_b, rn = 1/sum x^2
-//   (norm) or 1.  kappa = -y e^{-y phi} / (1 + e^{-y phi});
-//   loss = log(1 + e^{-y phi}).  Every slot (a, f) with a partner b != a in
+//   (norm) or 1.  With z = -y phi and e = exp(-|z|) (one exponential, never
+//   above 1, so a z past exp's range saturates instead of giving inf / inf):
+//   kappa = -y / (1 + e) if z > 0, else -y e / (1 + e);
+//   loss = max(z, 0) + log(1 + e).  (These are -y e^z / (1 + e^z) and
+//   log(1 + e^z).)  Every slot (a, f) with a partner b != a in
 //   field f, from the pre-step W:
 //   g = lam W[j_a][f] + kappa rn x_a sum_{b != a, f_b = f} x_b W[j_b][f_a];
 //   AdaGrad: G += g^2, W -= eta g / sqrt(G); plain SGD: W -= eta g.
@@ -125,9 +128,10 @@ double sgo_epoch(uint64_t P, const uint32_t *pu, const uint32_t *pv, uint32_t nn
         phi += t * x[a] * x[b];
       }
     phi *= rn;
-    const float ex = std::exp(-y * phi);
-    loss_sum += std::log1p((double)ex);
-    const float kappa = -y * ex / (1.0f + ex);
+    const float z = -y * phi;
+    const float ex = std::exp(-std::fabs(z));
+    loss_sum += (double)std::max(z, 0.0f) + std::log1p((double)ex);
+    const float kappa = -y * (z > 0 ? 1.0f / (1.0f + ex) : ex / (1.0f + ex));
     // every slot's step from the pre-step W, then the writes (slot order)
     wp.clear();
     gp.clear();
