@@ -350,6 +350,50 @@ int ocffm_eval_from_ranks(uint64_t m, const uint64_t *yptr, const uint32_t *rank
 int ocffm_problem_evaluate(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
                            uint32_t ncut, ocffm_eval *out);
 
+/* Label ranks among per-row candidate lists (no reference counterpart): the
+ * sampled-negatives protocol ("1 positive + 99 / 999 sampled negatives") and
+ * the short-list of a retrieval stage.  ocffm_problem_label_ranks with each
+ * row ranked among its own list instead of among every item.  Covers all X.m
+ * rows; the list of row i is ccol[cptr[i] .. cptr[i + 1]), in any order and
+ * with repeats: cptr holds X.m + 1 non-decreasing offsets with cptr[0] == 0.
+ * ranks, scores (may be NULL), ncand (may be NULL): as in
+ * ocffm_problem_label_ranks.  Does not change the solver state.
+ *  - Candidate set K_i of row i.  A candidate is defined as in
+ *    ocffm_problem_label_ranks: < n, or < npop on a cold row, and not among
+ *    seen's labels of row i.  K_i is the distinct entries of the list that are
+ *    candidates, united with the row's own labels that are candidates: the
+ *    positive is ranked whether or not the caller put it in the list.  A
+ *    duplicate counts once; other entries are ignored.
+ *  - Rank of a label: the 0-based number of members of K_i before it in
+ *    ocffm_problem_recommend's total order (score descending, equal scores by
+ *    ascending item index).  The other labels of the row count, as in
+ *    label_ranks.  ncand[i] = |K_i| for every row; an empty list gives the
+ *    number of the row's candidate labels.  Labels that are no candidates get
+ *    OCFFM_RANK_NONE and -inf; copies of a label share a rank.
+ *  - Scores: the value ocffm_problem_score returns for that pair, bit for bit.
+ *  - Reproducibility: ranks, scores and ncand do not depend on the order of
+ *    the list, on OCFFM_REC_ROWS, on OCFFM_REC_SEG nor on scheduling: K_i is a
+ *    set, built on the host, and all cross-wave accumulation is integer adds.
+ *  - Consequence: when every list holds all of 0..n-1, the three outputs
+ *    equal ocffm_problem_label_ranks's.
+ *  - Cost: the item rows of K_i are gathered, for the rows that have a
+ *    candidate label; a row without one is only counted.  No sweep over the n
+ *    items takes place.  There is no cap on a row's list.
+ *  - Errors: those of ocffm_problem_label_ranks, and OCFFM_E_ARG for a NULL
+ *    cptr, cptr[0] != 0, a decreasing cptr, or a NULL ccol with cptr[m] > 0.
+ *    X.m == 0 is OCFFM_OK.
+ *  - Sharded problems: as ocffm_problem_recommend_among.
+ * ocffm_problem_evaluate_among is this followed by ocffm_eval_from_ranks,
+ * with the errors of both.  The launches belong to the kernel family
+ * "evaluate"; the counter "eval_setup_us" holds the last call's host-side
+ * set-up time (the construction of the K_i included). */
+int ocffm_problem_label_ranks_among(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen,
+                                    const uint64_t *cptr, const uint32_t *ccol, uint32_t *ranks, double *scores,
+                                    uint32_t *ncand);
+int ocffm_problem_evaluate_among(ocffm_problem *p, const ocffm_data *X, const ocffm_data *seen,
+                                 const uint64_t *cptr, const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut,
+                                 ocffm_eval *out);
+
 /* print_epoch_info (ffm.cpp:1130-1145) of the last validation, and the
  * header of init_va (ffm.cpp:901-912), to stdout. */
 int ocffm_print_header(void);
@@ -535,8 +579,7 @@ int ocffm_sgd_sync(ocffm_sgd *s);
  *  - Sharded trainers: every rank holds a whole W, so each rank serves the
  *    rows it is given from its own current W; X is not sharded.  This has
  *    only been run on one rank.
- * Out of this path: candidate lists and pair scores (recommend_among, score)
- * and fp64. */
+ * Out of this path: fp64. */
 int ocffm_sgd_recommend(ocffm_sgd *s, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
                         uint32_t flags, uint32_t *items, double *scores);
 /* Exact label ranks under the current W: ocffm_problem_label_ranks on the SGD
@@ -562,12 +605,42 @@ int ocffm_sgd_label_ranks(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *s
  * errors it shares: the cuts, NULL out). */
 int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
                        uint32_t ncut, ocffm_eval *out);
+/* Pair scores and candidate lists on the SGD model: the Newton entries
+ * (ocffm_problem_score, ocffm_problem_recommend_among,
+ * ocffm_problem_label_ranks_among, ocffm_problem_evaluate_among) with their
+ * shape, order, short-row and duplicate rules, on ocffm_sgd_recommend's
+ * scores: a (row, item) pair has the bits ocffm_sgd_recommend and
+ * ocffm_sgd_label_ranks give it.
+ *  - There are no cold rows: candidates are the items < V.m (minus the row's
+ *    own labels under OCFFM_REC_EXCLUDE_LABELS, or seen's labels of the row).
+ *    ocffm_sgd_score gives -inf for pitem[e] >= V.m.
+ *  - The item side comes from the same cache that follows the model version
+ *    ("rank_item_builds" rises once per model change, not per call).
+ *  - ocffm_sgd_label_ranks_among: when every list holds all of 0..V.m-1 the
+ *    three outputs equal ocffm_sgd_label_ranks's.
+ *  - Reproducibility: as the Newton entries (OCFFM_REC_ROWS and OCFFM_REC_SEG
+ *    are read at create).
+ *  - Errors: those of ocffm_sgd_recommend (label ranks: ocffm_sgd_label_ranks;
+ *    evaluate: ocffm_sgd_evaluate), OCFFM_E_ARG for a NULL cptr, cptr[0] != 0,
+ *    a decreasing cptr, or a NULL ccol with cptr[rows] > 0; for the pairs
+ *    OCFFM_E_ARG for prow[e] >= X.m or a NULL prow / pitem / out with
+ *    npairs > 0 (every row of X is checked and laid out).  npairs == 0,
+ *    rows == 0 and X.m == 0 are OCFFM_OK.
+ * The counters are ocffm_sgd_counter's: "rank_setup_us", "rank_kernel_us". */
+int ocffm_sgd_score(ocffm_sgd *s, const ocffm_data *X, uint64_t npairs, const uint32_t *prow, const uint32_t *pitem,
+                    double *out);
+int ocffm_sgd_recommend_among(ocffm_sgd *s, const ocffm_data *X, uint64_t row0, uint64_t rows, const uint64_t *cptr,
+                              const uint32_t *ccol, uint32_t topn, uint32_t flags, uint32_t *items, double *scores);
+int ocffm_sgd_label_ranks_among(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                                const uint32_t *ccol, uint32_t *ranks, double *scores, uint32_t *ncand);
+int ocffm_sgd_evaluate_among(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                             const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out);
 /* Serving counters; an unknown name reads 0 (as ocffm_problem_counter).
  *  rank_item_builds    item-side projections since create
  *  rank_setup_us       the last serving call's host set-up (the item-side
  *                      projection included when it ran)
  *  rank_item_build_us  the last item-side projection
- *  rank_kernel_us      the last call's sweep, merge and label-score launches,
+ *  rank_kernel_us      the last call's sweep, list, merge and pair-score launches,
  *                      between HIP events on the trainer's stream */
 int ocffm_sgd_counter(ocffm_sgd *s, const char *name, int64_t *value);
 void ocffm_sgd_destroy(ocffm_sgd *s);

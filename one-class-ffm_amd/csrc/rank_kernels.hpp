@@ -1,5 +1,5 @@
 // rank_kernels.hpp — the serving kernels: top-N recommendation, ranking
-// evaluation, top-N among candidate lists.  Included through rank_driver.hpp
+// evaluation, top-N and label ranks among candidate lists.  Included through rank_driver.hpp
 // by solver.hip (the block Newton-CG problem: NORM = false) and by sgd.hip
 // (the SGD trainer's model: NORM = true), after kernels.hpp.
 #pragma once
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
 // row on the A side and of candidate l & 15's item row on the B side
 // (k_eval_label_scores's operand layout with one row for all 16 pairs), and
 // runs k_rec_topn's chain: chunks in order, four MFMAs per chunk, then
-// (acc + b_j) + a_i.  Every row of the 16 x 16 product is the query row, so
+// rec_score.  Every row of the 16 x 16 product is the query row, so
 // each lane reads candidate l & 15's score from its first D register; an
 // output element depends only on its own row and item, hence the bits are
 // those of recommend.  The query row's first RR_NA chunks stay in registers
@@ -599,6 +599,7 @@ template <typename real> struct RerankArgs {
   const double *popular;
   const int64_t *lptr;         // sorted, distinct labels < n of each row of the call (exclude)
   const uint32_t *lcol;
+  const real *su, *sv;         // NORM: squared norms of the call's rows, of the items
   const int64_t *wptr;         // per row of the call: its work items [wptr[i], wptr[i + 1])
   const uint32_t *wrow;        // work item -> row of the call
   const uint64_t *wbeg;        // work item -> its first list entry (an index of the call's ccol)
@@ -608,7 +609,7 @@ template <typename real> struct RerankArgs {
   uint32_t *part_j, *out_j;
 };
 
-template <typename real, int KP>
+template <typename real, int KP, bool NORM = false>
 __global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
   using M = RecMma<real>;
   using V = typename M::V;
@@ -627,6 +628,7 @@ __global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
 #pragma unroll
   for (int c = 0; c < RR_NA; c++) aq[c] = rec_ld<real, KP>(g.P, i, c, q, depth, !cold);
   const real ai = g.a[i];
+  const real sui = NORM ? g.su[i] : (real)0;
   const int64_t lb = g.exclude ? g.lptr[i] : 0, le = g.exclude ? g.lptr[i + 1] : 0;
   double v0 = REC_NEG_INF, v1 = REC_NEG_INF, tv = REC_NEG_INF;
   uint32_t j0 = REC_NONE, j1 = REC_NONE, tj = REC_NONE;
@@ -657,7 +659,7 @@ __global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
 #pragma unroll
         for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
       }
-      if (valid) v = (double)((acc[0] + g.b[j]) + ai);
+      if (valid) v = (double)rec_score<NORM>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
     }
     const bool cand = valid && q == 0 && rec_better(v, j, tv, tj);
     rec_offer<true>(__ballot(cand), v, j, v0, j0, v1, j1, tv, tj, g.topn, lane);
@@ -708,6 +710,133 @@ static __global__ __launch_bounds__(BLOCK) void k_rerank_merge(uint64_t R, uint6
     scores[il * topn + lane + 64] = v1;
     items[il * topn + lane + 64] = j1;
   }
+}
+
+// ------------------------------------- label ranks among candidate lists ---
+// Exact rank of every label among its row's own candidate set
+// (ocffm_problem_label_ranks_among): k_rerank's gather with k_eval_count's
+// counters in place of the list.
+//
+// k_rerank_count: one wave owns one work item, a segment of one row's
+// candidate set K_i, and walks it 16 entries at a time with k_rerank's
+// operand layout, resident query chunks (RR_NA) and chain, then rec_score: an
+// entry's score has recommend's bits.  The host hands over K_i itself (the
+// distinct list entries that are candidates, united with the row's candidate
+// labels: rank_driver.hpp), so every entry counts, once.  An entry (s_ij, j)
+// is located among the row's labels, which are sorted by the ranking order
+// (kv / kj): one compare against the row's last label drops an entry that
+// ranks before none, a binary search finds the first label the others rank
+// strictly before, and that label's counter gets one more.  The prefix sum of
+// a row's counters is then each label's rank.  Adds of one step to one
+// counter are merged, and a run of steps that all go to the same counter (the
+// usual case: one positive per row) is held in a wave-uniform register and
+// added once.  Cold rows take popular[j] and gather nothing.  Integer adds
+// commute: the result does not depend on the list's order, on how it was cut
+// into segments or on scheduling.
+// Ragged edges: entries outside a work item's range are never read, nor are
+// item rows of lanes past the segment's end.
+template <typename real> struct RerankCountArgs {
+  uint64_t W, w0;              // work items of this launch; the first one's index in wrow / wbeg / wlen
+  uint64_t c0;                 // first entry of this launch in the call's sets (ccol is relative to it)
+  int C;
+  const real *const *P;        // C user-side cross tables of the call's rows
+  const real *const *Q;        // C item-side cross tables (n x KP)
+  const real *a, *b;           // a_i of the call's rows, b_j
+  const uint8_t *cold;         // per row of the call
+  const double *popular;
+  const real *su, *sv;         // NORM: squared norms of the call's rows, of the items
+  const uint32_t *wrow;        // work item -> row of the call
+  const uint64_t *wbeg;        // work item -> its first entry (an index of the call's sets)
+  const uint32_t *wlen;        // work item -> entries
+  const uint32_t *ccol;        // this launch's entries (entry c0 first): distinct candidates of their row
+  const int64_t *kptr;         // each row's labels in kv / kj / cnt (a row with work items has some)
+  const double *kv;            // label scores and items, each row's sorted by the ranking order
+  const uint32_t *kj;
+  uint32_t *cnt;               // per label: candidates between the label before it and itself
+};
+
+template <typename real, int KP, bool NORM = false>
+__global__ __launch_bounds__(BLOCK) void k_rerank_count(RerankCountArgs<real> g) {
+  using M = RecMma<real>;
+  using V = typename M::V;
+  const int lane = threadIdx.x & 63;
+  const int m = lane & 15, q = lane >> 4;
+  const uint64_t wl = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+  if (wl >= g.W) return;  // (wave-uniform)
+  const uint64_t w = g.w0 + wl;
+  const uint64_t i = g.wrow[w];
+  const uint64_t cb = g.wbeg[w] - g.c0;
+  const uint32_t len = g.wlen[w];
+  const int64_t kb = g.kptr[i];
+  const int np = (int)(g.kptr[i + 1] - kb);
+  if (np <= 0 || len == 0) return;  // (wave-uniform; the host makes no such work item)
+  const bool cold = g.cold[i] != 0;
+  const int depth = g.C * KP, nch = (depth + 15) / 16;
+  V aq[RR_NA];
+#pragma unroll
+  for (int c = 0; c < RR_NA; c++) aq[c] = rec_ld<real, KP>(g.P, i, c, q, depth, !cold);
+  const real ai = g.a[i];
+  const real sui = NORM ? g.su[i] : (real)0;
+  const double last_v = g.kv[kb + np - 1];
+  const uint32_t last_j = g.kj[kb + np - 1];
+  int pt = -1;      // the counter the pending adds go to (wave-uniform)
+  uint32_t pn = 0;  // pending adds
+  uint32_t jn = (uint32_t)m < len ? g.ccol[cb + m] : REC_NONE;
+  for (uint32_t t0 = 0; t0 < len; t0 += 16) {
+    const bool have = t0 + m < len;
+    const uint32_t j = jn;
+    // the next 16 entries are on their way while these are scored
+    jn = (uint64_t)t0 + 16 + m < len ? g.ccol[cb + t0 + 16 + m] : REC_NONE;
+    double v = REC_NEG_INF;
+    if (cold) {
+      if (have) v = g.popular[j];
+    } else {
+      V bq[RR_NA];
+#pragma unroll
+      for (int c = 0; c < RR_NA; c++) bq[c] = rec_ld<real, KP>(g.Q, j, c, q, depth, have);
+      V acc = {(real)0, (real)0, (real)0, (real)0};
+#pragma unroll
+      for (int c = 0; c < RR_NA; c++)
+        if (c < nch) {
+#pragma unroll
+          for (int s = 0; s < 4; s++) acc = M::mma(aq[c][s], bq[c][s], acc);
+        }
+      for (int c = RR_NA; c < nch; c++) {
+        const V av = rec_ld<real, KP>(g.P, i, c, q, depth, true), bv = rec_ld<real, KP>(g.Q, j, c, q, depth, have);
+#pragma unroll
+        for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
+      }
+      if (have) v = (double)rec_score<NORM>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
+    }
+    // counting: the last label first, so the search runs on few entries
+    const bool cand = have && q == 0 && rec_better(v, j, last_v, last_j);
+    const uint64_t mask = __ballot(cand);
+    if (!mask) continue;
+    int t = 0;
+    if (cand) {  // the first label it ranks before (it ranks before the last one)
+      int lo = 0, hi = np - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rec_better(v, j, g.kv[kb + mid], g.kj[kb + mid])) hi = mid;
+        else lo = mid + 1;
+      }
+      t = lo;
+    }
+    const int first = __ffsll((unsigned long long)mask) - 1;
+    const int tf = (int)rec_lane((uint32_t)t, first);
+    const bool one = __ballot(cand && t != tf) == 0;  // the whole step before the same label
+    if (one) {
+      if (tf != pt) {
+        if (pn && lane == 0) atomicAdd(g.cnt + kb + pt, pn);
+        pt = tf;
+        pn = 0;
+      }
+      pn += (uint32_t)__popcll(mask);
+    } else if (cand) {
+      atomicAdd(g.cnt + kb + t, 1u);
+    }
+  }
+  if (pn && lane == 0) atomicAdd(g.cnt + kb + pt, pn);
 }
 
 }  // namespace ocffm

@@ -408,6 +408,7 @@ class Trainer {
     off_ = off;
     if (const char *e = std::getenv("OCFFM_REC_SLICES")) rec_slices_ = (unsigned)std::clamp(std::atoi(e), 1, 256);
     if (const char *e = std::getenv("OCFFM_REC_ROWS")) rec_rows_ = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    rec_seg_ = RankModel<float>::seg_from_env();
     {
       int ncu = 0;
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, prm.device) != hipSuccess) ncu = 1;
@@ -634,13 +635,64 @@ class Trainer {
     Rank{*this, m}.recommend(L, rows, topn, excl, items, scores, "rank_setup_us");
     counters_["rank_kernel_us"] = (int64_t)kernel_us_;
   }
-  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores, uint32_t *ncand) {
-    serve_check();
+  static void label_check(const HostData &X, const HostData *seen, const uint32_t *ranks) {
     if (!ranks) throw Error(OCFFM_E_ARG, "null ranks");
     if (!X.has_label || X.yptr.size() != X.m + 1) throw Error(OCFFM_E_ARG, "X has no labels");
     if (seen && (seen->m != X.m || (seen->m && seen->yptr.size() != seen->m + 1)))
       throw Error(OCFFM_E_ARG, "seen must have X's row count (and labels)");
     if (X.m >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many rows");
+  }
+  // The list path on the SGD model (ocffm.h ocffm_sgd_score,
+  // ocffm_sgd_recommend_among, ocffm_sgd_label_ranks_among): the argument
+  // checks and the rows' layout here, the rest in the driver.
+  void score(const HostData &X, uint64_t npairs, const uint32_t *prow, const uint32_t *pitem, double *out) {
+    serve_check();
+    if (npairs && (!prow || !pitem || !out)) throw Error(OCFFM_E_ARG, "null pair or output array");
+    for (uint64_t e = 0; e < npairs; e++)
+      if (prow[e] >= X.m) throw Error(OCFFM_E_ARG, "pair row outside X");
+    check_rows(X, 0, X.m);
+    if (npairs == 0) return;
+    serve_begin();
+    Query L;
+    layout(L, X, 0, X.m, nullptr);
+    const RankModel<float> m = model();
+    Rank{*this, m}.score(L, npairs, prow, pitem, out, "rank_setup_us");
+    counters_["rank_kernel_us"] = (int64_t)kernel_us_;
+  }
+  void recommend_among(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol,
+                       uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+    serve_check();
+    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
+    if (row0 > X.m || rows > X.m - row0) throw Error(OCFFM_E_ARG, "row range outside X");
+    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    check_lists(cptr, ccol, rows);
+    check_rows(X, row0, rows);
+    if (rows == 0) return;
+    serve_begin();
+    const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
+    Query L;
+    layout(L, X, row0, rows, excl ? &X : nullptr);
+    const RankModel<float> m = model();
+    Rank{*this, m}.rerank(L, rows, cptr, ccol, topn, excl, items, scores, "rank_setup_us");
+    counters_["rank_kernel_us"] = (int64_t)kernel_us_;
+  }
+  void label_ranks_among(const HostData &X, const HostData *seen, const uint64_t *cptr, const uint32_t *ccol,
+                         uint32_t *ranks, double *scores, uint32_t *ncand) {
+    serve_check();
+    label_check(X, seen, ranks);
+    check_lists(cptr, ccol, X.m);
+    check_rows(X, 0, X.m);
+    if (X.m == 0) return;
+    serve_begin();
+    Query L;
+    layout(L, X, 0, X.m, seen);
+    const RankModel<float> m = model();
+    Rank{*this, m}.label_ranks_among(L, X, cptr, ccol, ranks, scores, ncand, "rank_setup_us");
+    counters_["rank_kernel_us"] = (int64_t)kernel_us_;
+  }
+  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores, uint32_t *ncand) {
+    serve_check();
+    label_check(X, seen, ranks);
     check_rows(X, 0, X.m);
     if (X.m == 0) return;
     serve_begin();
@@ -742,6 +794,7 @@ class Trainer {
     m.kp = kp_;
     m.slices = rec_slices_;
     m.chunk_rows = rec_rows_;
+    m.rec_seg = rec_seg_;
     m.stream = stream_;
     return m;
   }
@@ -901,6 +954,7 @@ class Trainer {
   std::vector<uint64_t> off_;      // first global feature id of each field
   unsigned rec_slices_ = 0;        // OCFFM_REC_SLICES (0: from n, the rows and the CU count)
   uint64_t rec_rows_ = 0;          // OCFFM_REC_ROWS (0: 4096 rows per chunk)
+  uint64_t rec_seg_ = 0;           // OCFFM_REC_SEG (0: from the call's entries and the resident waves)
   unsigned ncu_ = 1;
   uint64_t version_ = 1;           // of W: epoch, average and set_w advance it
   uint64_t item_version_ = 0;      // the version item_ was projected from
@@ -988,8 +1042,23 @@ int ocffm_sgd_label_ranks(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *s
   SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X");
            s->t->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand));
 }
-int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut,
-                       ocffm_eval *out) {
+int ocffm_sgd_score(ocffm_sgd *s, const ocffm_data *X, uint64_t npairs, const uint32_t *prow, const uint32_t *pitem,
+                    double *out) {
+  SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X"); s->t->score(X->d, npairs, prow, pitem, out));
+}
+int ocffm_sgd_recommend_among(ocffm_sgd *s, const ocffm_data *X, uint64_t row0, uint64_t rows, const uint64_t *cptr,
+                              const uint32_t *ccol, uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+  SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X");
+           s->t->recommend_among(X->d, row0, rows, cptr, ccol, topn, flags, items, scores));
+}
+int ocffm_sgd_label_ranks_among(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                                const uint32_t *ccol, uint32_t *ranks, double *scores, uint32_t *ncand) {
+  SGD_CALL(if (!X) throw ocffm::Error(OCFFM_E_ARG, "null X");
+           s->t->label_ranks_among(X->d, seen ? &seen->d : nullptr, cptr, ccol, ranks, scores, ncand));
+}
+// among: the labels are ranked among the lists (cptr, ccol), else among every item
+static int sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, bool among, const uint64_t *cptr,
+                        const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
   std::vector<uint32_t> ranks, ncand;
   std::vector<double> scores;
   const int st = guarded([&] {
@@ -1005,10 +1074,20 @@ int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen
     ranks.resize(d.ycol.size() + 1);
     ncand.resize(d.m + 1);
     scores.resize(d.ycol.size() + 1);
-    s->t->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data());
+    const ocffm::HostData *sn = seen ? &seen->d : nullptr;
+    if (among) s->t->label_ranks_among(d, sn, cptr, ccol, ranks.data(), scores.data(), ncand.data());
+    else s->t->label_ranks(d, sn, ranks.data(), scores.data(), ncand.data());
   });
   if (st != OCFFM_OK) return st;
   return ocffm_eval_from_ranks(X->d.m, X->d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+}
+int ocffm_sgd_evaluate(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut,
+                       ocffm_eval *out) {
+  return sgd_evaluate(s, X, seen, false, nullptr, nullptr, cuts, ncut, out);
+}
+int ocffm_sgd_evaluate_among(ocffm_sgd *s, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                             const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
+  return sgd_evaluate(s, X, seen, true, cptr, ccol, cuts, ncut, out);
 }
 int ocffm_sgd_counter(ocffm_sgd *s, const char *name, int64_t *value) {
   SGD_CALL(if (!name || !value) throw ocffm::Error(OCFFM_E_ARG, "null argument"); *value = s->t->counter(name));

@@ -331,6 +331,8 @@ struct ProblemBase {
   virtual void recommend_among(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr,
                                const uint32_t *ccol, uint32_t topn, uint32_t flags, uint32_t *items,
                                double *scores) = 0;
+  virtual void label_ranks_among(const HostData &X, const HostData *seen, const uint64_t *cptr, const uint32_t *ccol,
+                                 uint32_t *ranks, double *scores, uint32_t *ncand) = 0;
   virtual uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) = 0;
   virtual void set(char what, uint32_t b12, const double *in, uint64_t len) = 0;
   virtual void grad(uint32_t f1, uint32_t f2, int half, double *out) = 0;
@@ -391,8 +393,7 @@ template <typename real> class Problem final : public ProblemBase {
     if (const char *e = std::getenv("OCFFM_NO_OWNED")) no_owned_ = std::atoi(e) != 0;  // all-reduce every field
     if (const char *e = std::getenv("OCFFM_REC_SLICES")) rec_slices_ = (unsigned)std::clamp(std::atoi(e), 1, 256);
     if (const char *e = std::getenv("OCFFM_REC_ROWS")) rec_rows_ = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
-    if (const char *e = std::getenv("OCFFM_REC_SEG"))
-      rec_seg_ = (std::clamp<uint64_t>(std::strtoull(e, nullptr, 10), 1, 1u << 30) + 15) / 16 * 16;
+    rec_seg_ = RankModel<real>::seg_from_env();
     // shard users contiguously
     u0_ = U.m * (uint64_t)comm_.rank / (uint64_t)comm_.nranks;
     u1_ = U.m * (uint64_t)(comm_.rank + 1) / (uint64_t)comm_.nranks;
@@ -1085,6 +1086,7 @@ template <typename real> class Problem final : public ProblemBase {
     m.kp = kp_;
     m.slices = rec_slices_;
     m.chunk_rows = rec_rows_;
+    m.rec_seg = rec_seg_;
     m.stream = stream_;
     return m;
   }
@@ -1103,14 +1105,17 @@ template <typename real> class Problem final : public ProblemBase {
   // Exact rank of every label of X among its row's candidates (ocffm.h
   // ocffm_problem_label_ranks): the rows' layout, then the driver's
   // label_ranks.
-  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
-                   uint32_t *ncand) override {
-    need_init();
+  static void label_check(const HostData &X, const HostData *seen, const uint32_t *ranks) {
     if (!ranks) throw Error(OCFFM_E_ARG, "null ranks");
     if (!X.has_label || X.yptr.size() != X.m + 1) throw Error(OCFFM_E_ARG, "X has no labels");
     if (seen && (seen->m != X.m || (seen->m && seen->yptr.size() != seen->m + 1)))
       throw Error(OCFFM_E_ARG, "seen must have X's row count (and labels)");
     if (X.m >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many rows");
+  }
+  void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
+                   uint32_t *ncand) override {
+    need_init();
+    label_check(X, seen, ranks);
     const uint64_t rows = X.m;
     rec_check(X, 0, rows);
     if (rows == 0) return;
@@ -1146,8 +1151,8 @@ template <typename real> class Problem final : public ProblemBase {
   }
 
   // ------------------------------------------------ scores of given pairs
-  // Scores of (row of X, item) pairs (ocffm.h ocffm_problem_score): the pairs
-  // that are candidates go through k_eval_label_scores, the others are -inf.
+  // Scores of (row of X, item) pairs (ocffm.h ocffm_problem_score): the rows'
+  // layout, then the driver's score.
   void score(const HostData &X, uint64_t npairs, const uint32_t *prow, const uint32_t *pitem,
              double *out) override {
     need_init();
@@ -1161,49 +1166,19 @@ template <typename real> class Problem final : public ProblemBase {
     rank_t0_ = std::chrono::steady_clock::now();
     RecRows L;
     rec_layout(L, X, 0, X.m, nullptr);
-    const uint64_t npop = std::min<uint64_t>(npop_, n_);
-    std::vector<uint32_t> krow, kitem;
-    std::vector<uint64_t> where;
-    for (uint64_t e = 0; e < npairs; e++) {
-      out[e] = -std::numeric_limits<double>::infinity();
-      if (pitem[e] >= (L.cold[prow[e]] ? npop : n_)) continue;
-      krow.push_back(prow[e]);
-      kitem.push_back(pitem[e]);
-      where.push_back(e);
-    }
-    sync();
-    rank_setup_done("rec_setup_us");
-    if (kitem.empty()) return;
     const RankModel<real> m = rank_model();
-    const std::vector<double> kv = Rank{*this, m}.score_pairs(L, krow, kitem, "rerank");
-    flush_prof();
-    for (size_t t = 0; t < kv.size(); t++) out[where[t]] = kv[t];
+    Rank{*this, m}.score(L, npairs, prow, pitem, out, "rec_setup_us");
   }
 
   // ------------------------------------------ top-N among candidate lists
   // Top-N of each row's own candidate list (ocffm.h
-  // ocffm_problem_recommend_among).  Every list is cut into segments, one
-  // k_rerank work item (a wave) each, so a long list does not serialise on
-  // one wave; nothing is sorted on the host.  The rows go in chunks: scratch
-  // is a chunk's work items x topn partial entries.
-  // Segment length (OCFFM_REC_SEG forces it): every segment pays its own list
-  // warm-up (about topn (1 + ln(len / topn)) inserts), so as few segments as
-  // fill the machine: the call's entries over the resident waves, within
-  // REC_SEG_MIN..REC_SEG_MAX.  Measured at the kkbox shape (3,075 rows, fp32,
-  // family ms at 1,000 / 10,000 entries per row): 128: 1.44 / 8.49,
-  // 256: 1.28 / 7.36, 512: 1.07 / 6.61, 1024: 0.87 / 6.07, 2048: 0.86 / 6.01.
-  // Below 256 the one-wave merge of a row's partial lists takes over (64 rows
-  // x 10,000 entries: 0.88 ms at 64, 0.61 at 128, 0.33 at 256, 0.39 at 512).
-  static constexpr uint64_t REC_SEG_MIN = 256, REC_SEG_MAX = 2048;
+  // ocffm_problem_recommend_among): the rows' layout, then the driver's
+  // rerank.
   void recommend_among(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol,
                        uint32_t topn, uint32_t flags, uint32_t *items, double *scores) override {
     need_init();
     rec_check_topn(X, row0, rows, topn, items);
-    if (!cptr) throw Error(OCFFM_E_ARG, "null cptr");
-    if (cptr[0] != 0) throw Error(OCFFM_E_ARG, "cptr[0] must be 0");
-    for (uint64_t i = 0; i < rows; i++)
-      if (cptr[i + 1] < cptr[i]) throw Error(OCFFM_E_ARG, "cptr must not decrease");
-    if (cptr[rows] > 0 && !ccol) throw Error(OCFFM_E_ARG, "null ccol");
+    check_lists(cptr, ccol, rows);
     rec_check(X, row0, rows);
     if (rows == 0) return;
     sync_owned();
@@ -1213,102 +1188,27 @@ template <typename real> class Problem final : public ProblemBase {
     RecRows L;
     rec_layout(L, X, row0, rows, excl ? &X : nullptr);
     const RankModel<real> m = rank_model();
-    Rank drv{*this, m};
-    // work items: row-major, a row's segments in list order
-    uint64_t seg = rec_seg_;
-    if (!seg) {
-      const unsigned slots = drv.resident([](auto K) { return k_rerank<real, decltype(K)::value>; });
-      seg = cptr[rows] / ((uint64_t)slots * (BLOCK / 64)) + 1;
-      seg = (std::clamp(seg, REC_SEG_MIN, REC_SEG_MAX) + 15) / 16 * 16;
-    }
-    std::vector<int64_t> wptr(rows + 1, 0);
-    std::vector<uint32_t> wrow, wlen;
-    std::vector<uint64_t> wbeg;
-    for (uint64_t i = 0; i < rows; i++) {
-      for (uint64_t b = cptr[i]; b < cptr[i + 1]; b += seg) {
-        wrow.push_back((uint32_t)i);
-        wbeg.push_back(b);
-        wlen.push_back((uint32_t)std::min<uint64_t>(seg, cptr[i + 1] - b));
-      }
-      wptr[i + 1] = (int64_t)wrow.size();
-    }
-    const uint64_t chunk = drv.chunk(rows);
-    uint64_t maxw = 0, maxc = 0;
-    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
-      const uint64_t c1 = std::min(rows, c0 + chunk);
-      maxw = std::max<uint64_t>(maxw, (uint64_t)(wptr[c1] - wptr[c0]));
-      maxc = std::max<uint64_t>(maxc, cptr[c1] - cptr[c0]);
-    }
-    DevBuf<int64_t> dwptr;
-    DevBuf<uint32_t> dwrow, dwlen, dccol, part_j, out_j;
-    DevBuf<uint64_t> dwbeg;
-    DevBuf<double> part_v, out_v;
-    dwptr.upload(wptr);
-    if (wrow.empty()) {  // (a pointer for a call without list entries)
-      wrow.push_back(0);
-      wbeg.push_back(0);
-      wlen.push_back(0);
-    }
-    dwrow.upload(wrow);
-    dwbeg.upload(wbeg);
-    dwlen.upload(wlen);
-    dccol.alloc(std::max<uint64_t>(maxc, 1), false);
-    part_v.alloc(std::max<uint64_t>(maxw, 1) * topn, false);
-    part_j.alloc(std::max<uint64_t>(maxw, 1) * topn, false);
-    out_v.alloc(chunk * topn, false);
-    out_j.alloc(chunk * topn, false);
+    Rank{*this, m}.rerank(L, rows, cptr, ccol, topn, excl, items, scores, "rec_setup_us");
+  }
+
+  // Exact rank of every label of X among its row's own candidate list (ocffm.h
+  // ocffm_problem_label_ranks_among): label_ranks' checks and layout, then the
+  // driver's label_ranks_among.
+  void label_ranks_among(const HostData &X, const HostData *seen, const uint64_t *cptr, const uint32_t *ccol,
+                         uint32_t *ranks, double *scores, uint32_t *ncand) override {
+    need_init();
+    label_check(X, seen, ranks);
+    check_lists(cptr, ccol, X.m);
+    const uint64_t rows = X.m;
+    rec_check(X, 0, rows);
+    if (rows == 0) return;
+    sync_owned();
     sync();
-    rank_setup_done("rec_setup_us");
-    for (uint64_t c0 = 0; c0 < rows; c0 += chunk) {
-      const uint64_t cr = std::min(chunk, rows - c0);
-      const uint64_t nc = cptr[c0 + cr] - cptr[c0];
-      if (nc) HIPCHK(hipMemcpyAsync(dccol.p, ccol + cptr[c0], nc * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-      RerankArgs<real> g{};
-      g.W = (uint64_t)(wptr[c0 + cr] - wptr[c0]);
-      g.w0 = (uint64_t)wptr[c0];
-      g.r0 = c0;
-      g.c0 = cptr[c0];
-      g.n = n_;
-      g.npop = std::min<uint64_t>(npop_, n_);
-      g.C = (int)C_;
-      g.topn = (int)topn;
-      g.exclude = excl ? 1 : 0;
-      g.P = L.pt.p;
-      g.Q = tabs_.p + C_;
-      g.a = L.ax.p;
-      g.b = V_.bias.p;
-      g.cold = L.dcold.p;
-      g.popular = popular_.p;
-      g.lptr = L.dlptr.p;
-      g.lcol = L.dlcol.p;
-      g.wptr = dwptr.p;
-      g.wrow = dwrow.p;
-      g.wbeg = dwbeg.p;
-      g.wlen = dwlen.p;
-      g.ccol = dccol.p;
-      g.part_v = part_v.p;
-      g.part_j = part_j.p;
-      g.out_v = out_v.p;
-      g.out_j = out_j.p;
-      const double depth = (double)C_ * kp_;
-      // gathered Q rows and b_j (an upper bound: every entry taken as a warm candidate), the rows' P, the
-      // lists and work items, the partial lists written and read back, the results
-      const double bytes = (double)nc * (depth * sizeof(real) + sizeof(real) + sizeof(uint32_t)) +
-                           (double)cr * depth * sizeof(real) +
-                           (double)g.W * (20.0 + 2.0 * topn * (sizeof(double) + sizeof(uint32_t))) +
-                           (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
-      prof_launch("rerank", bytes, [&] {
-        if (g.W)
-          with_kp(kp_, [&](auto K) {
-            constexpr int KP = decltype(K)::value;
-            launch(k_rerank<real, KP>, (unsigned)((g.W + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, g);
-          });
-        launch(k_rerank_merge, (unsigned)((cr + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, cr, c0, g.w0, (int)topn,
-               (const int64_t *)dwptr.p, (const double *)part_v.p, (const uint32_t *)part_j.p, out_j.p, out_v.p);
-      }, 2.0 * (double)nc * depth);
-      drv.copy_back(c0, cr, topn, out_j, out_v, items, scores);
-    }
-    flush_prof();
+    rank_t0_ = std::chrono::steady_clock::now();
+    RecRows L;
+    rec_layout(L, X, 0, rows, seen);
+    const RankModel<real> m = rank_model();
+    Rank{*this, m}.label_ranks_among(L, X, cptr, ccol, ranks, scores, ncand, "eval_setup_us");
   }
 
   // ----------------------------------------------------------- access
@@ -4532,6 +4432,12 @@ int ocffm_problem_recommend_among(ocffm_problem *prob, const ocffm_data *X, uint
   PROB_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
             prob->p->recommend_among(X->d, row0, rows, cptr, ccol, topn, flags, items, scores));
 }
+int ocffm_problem_label_ranks_among(ocffm_problem *prob, const ocffm_data *X, const ocffm_data *seen,
+                                    const uint64_t *cptr, const uint32_t *ccol, uint32_t *ranks, double *scores,
+                                    uint32_t *ncand) {
+  PROB_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
+            prob->p->label_ranks_among(X->d, seen ? &seen->d : nullptr, cptr, ccol, ranks, scores, ncand));
+}
 
 static void check_cuts(const uint32_t *cuts, uint32_t ncut) {
   if (!cuts || ncut < 1 || ncut > OCFFM_EVAL_MAX_CUTS) throw Error(OCFFM_E_ARG, "ncut must be in 1..OCFFM_EVAL_MAX_CUTS");
@@ -4620,6 +4526,21 @@ int ocffm_problem_evaluate(ocffm_problem *prob, const ocffm_data *X, const ocffm
     std::vector<uint32_t> ranks(d.ycol.size() + 1), ncand(d.m + 1);
     std::vector<double> scores(d.ycol.size() + 1);
     prob->p->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data());
+    eval_from_ranks(d.m, d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+  });
+}
+int ocffm_problem_evaluate_among(ocffm_problem *prob, const ocffm_data *X, const ocffm_data *seen,
+                                 const uint64_t *cptr, const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut,
+                                 ocffm_eval *out) {
+  return guarded([&] {
+    if (!prob || !prob->p) throw Error(OCFFM_E_ARG, "null problem");
+    if (!X) throw Error(OCFFM_E_ARG, "null X");
+    if (!out) throw Error(OCFFM_E_ARG, "null output");
+    check_cuts(cuts, ncut);
+    const HostData &d = X->d;
+    std::vector<uint32_t> ranks(d.ycol.size() + 1), ncand(d.m + 1);
+    std::vector<double> scores(d.ycol.size() + 1);
+    prob->p->label_ranks_among(d, seen ? &seen->d : nullptr, cptr, ccol, ranks.data(), scores.data(), ncand.data());
     eval_from_ranks(d.m, d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
   });
 }

@@ -16,7 +16,9 @@
 //   of every row's own list instead;
 //   --eval <file> [--eval-cuts c1,c2,...] [--eval-seen <file>]: after that,
 //   the ranking metrics of the model on the labelled rows of <file> (read
-//   like a -p file) as one `eval` table on stdout.
+//   like a -p file) as one `eval` table on stdout; with
+//   --eval-candidates <file> (--rec-candidates' format, one list per row of
+//   the --eval file) every label is ranked among its row's list and labels.
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -54,7 +56,9 @@ static std::string usage() {
          "                         the --recommend file, whitespace-separated; a blank line is an empty list)\n"
          "--eval <path>: after training, print ranking metrics on the labelled rows of this file (read like -p)\n"
          "--eval-cuts <c1,c2,...>: up to 8 increasing cut-offs (default 5,10,20,40,80)\n"
-         "--eval-seen <path>: rows whose labels are left out of the candidates (same row count as --eval)\n";
+         "--eval-seen <path>: rows whose labels are left out of the candidates (same row count as --eval)\n"
+         "--eval-candidates <path>: rank every label among its row's own list and labels only (line i: the item\n"
+         "                          indices of row i of the --eval file, in --rec-candidates' format)\n";
 }
 
 // train.cpp:22-32: at least one digit somewhere in the token.
@@ -64,9 +68,10 @@ static bool is_numerical(const char *s) {
   return false;
 }
 
-// --rec-candidates: one list per line.  Throws std::invalid_argument (exit 1).
-static void read_candidates(const std::string &path, std::uint64_t rows, std::vector<std::uint64_t> &cptr,
-                            std::vector<std::uint32_t> &ccol) {
+// --rec-candidates / --eval-candidates: one list per line of the file of
+// option `rows_of`.  Throws std::invalid_argument (exit 1).
+static void read_candidates(const std::string &path, const char *rows_of, std::uint64_t rows,
+                            std::vector<std::uint64_t> &cptr, std::vector<std::uint32_t> &ccol) {
   std::ifstream in(path);
   if (!in) throw std::invalid_argument("cannot read " + path);
   cptr.assign(1, 0);
@@ -91,7 +96,7 @@ static void read_candidates(const std::string &path, std::uint64_t rows, std::ve
   }
   if (cptr.size() - 1 != rows)
     throw std::invalid_argument(path + ": " + std::to_string(cptr.size() - 1) + " lines for " + std::to_string(rows) +
-                                " rows of the --recommend file");
+                                " rows of the " + rows_of + " file");
 }
 
 struct Fail : std::runtime_error {
@@ -106,7 +111,7 @@ static void check(int st) {
 int main(int argc, char **argv) {
   ocffm_param prm;
   ocffm_param_default(&prm);
-  std::string te_path, model_path, rec_path, rec_out, rec_cand, eval_path, eval_seen;
+  std::string te_path, model_path, rec_path, rec_out, rec_cand, eval_path, eval_seen, eval_cand;
   std::vector<uint32_t> eval_cuts{5, 10, 20, 40, 80};
   long topn = 10;
   bool rec_unseen = false;
@@ -141,6 +146,7 @@ int main(int argc, char **argv) {
       else if (a == "--rec-candidates") rec_cand = value(false, "need to specify path after --rec-candidates");
       else if (a == "--eval") eval_path = value(false, "need to specify path after --eval");
       else if (a == "--eval-seen") eval_seen = value(false, "need to specify path after --eval-seen");
+      else if (a == "--eval-candidates") eval_cand = value(false, "need to specify path after --eval-candidates");
       else if (a == "--eval-cuts") {
         eval_cuts.clear();
         for (const char *s = value(true, "need to specify cut-offs after --eval-cuts"); *s;) {
@@ -157,6 +163,7 @@ int main(int argc, char **argv) {
     if (!rec_cand.empty() && rec_path.empty()) throw std::invalid_argument("--rec-candidates needs --recommend <path>");
     if (topn < 1 || topn > OCFFM_REC_MAX_TOPN) throw std::invalid_argument("--topn must be in 1..128");
     if (!eval_seen.empty() && eval_path.empty()) throw std::invalid_argument("--eval-seen needs --eval <path>");
+    if (!eval_cand.empty() && eval_path.empty()) throw std::invalid_argument("--eval-candidates needs --eval <path>");
     if (eval_cuts.empty() || eval_cuts.size() > OCFFM_EVAL_MAX_CUTS) throw std::invalid_argument("--eval-cuts takes 1..8 cut-offs");
     for (size_t s = 1; s < eval_cuts.size(); s++)
       if (eval_cuts[s] <= eval_cuts[s - 1]) throw std::invalid_argument("--eval-cuts must be strictly increasing");
@@ -195,8 +202,21 @@ int main(int argc, char **argv) {
       check(ocffm_data_get_ds(U, ds.data()));
       check(ocffm_data_read(rec_path.c_str(), 1, ds.data(), (uint32_t)info.f, &Xrec));
       check(ocffm_data_get_info(Xrec, &xi));
-      read_candidates(rec_cand, xi.m, cptr, ccol);
+      read_candidates(rec_cand, "--recommend", xi.m, cptr, ccol);
       ccol.push_back(0);  // (a pointer for an empty file)
+    }
+    ocffm_data *Xev = nullptr;
+    std::vector<std::uint64_t> eptr;
+    std::vector<std::uint32_t> ecol;
+    if (!eval_cand.empty()) {
+      ocffm_data_info info, xi;
+      check(ocffm_data_get_info(U, &info));
+      std::vector<std::uint64_t> ds(info.f ? info.f : 1);
+      check(ocffm_data_get_ds(U, ds.data()));
+      check(ocffm_data_read(eval_path.c_str(), 1, ds.data(), (uint32_t)info.f, &Xev));
+      check(ocffm_data_get_info(Xev, &xi));
+      read_candidates(eval_cand, "--eval", xi.m, eptr, ecol);
+      ecol.push_back(0);
     }
     phase("read");
     ocffm_problem *prob = nullptr;
@@ -247,11 +267,15 @@ int main(int argc, char **argv) {
       check(ocffm_data_get_info(U, &info));
       std::vector<std::uint64_t> ds(info.f ? info.f : 1);
       check(ocffm_data_get_ds(U, ds.data()));
-      ocffm_data *X = nullptr, *Sn = nullptr;
-      check(ocffm_data_read(eval_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
+      ocffm_data *X = Xev, *Sn = nullptr;
+      if (!X) check(ocffm_data_read(eval_path.c_str(), 1, ds.data(), (uint32_t)info.f, &X));
       if (!eval_seen.empty()) check(ocffm_data_read(eval_seen.c_str(), 1, ds.data(), (uint32_t)info.f, &Sn));
       ocffm_eval ev;
-      check(ocffm_problem_evaluate(prob, X, Sn, eval_cuts.data(), (uint32_t)eval_cuts.size(), &ev));
+      if (eval_cand.empty())
+        check(ocffm_problem_evaluate(prob, X, Sn, eval_cuts.data(), (uint32_t)eval_cuts.size(), &ev));
+      else
+        check(ocffm_problem_evaluate_among(prob, X, Sn, eptr.data(), ecol.data(), eval_cuts.data(),
+                                           (uint32_t)eval_cuts.size(), &ev));
       std::printf("eval rows %llu rows_used %llu labels %llu labels_ranked %llu\n", (unsigned long long)ev.rows,
                   (unsigned long long)ev.rows_used, (unsigned long long)ev.labels, (unsigned long long)ev.labels_ranked);
       std::printf("eval loss %.17g mrr %.17g auc %.17g\n", ev.loss, ev.mrr, ev.auc);

@@ -85,7 +85,8 @@ EXPORTS = [
     "ocffm_problem_set", "ocffm_problem_grad", "ocffm_problem_hv", "ocffm_problem_save_model",
     "ocffm_problem_validate_forced", "ocffm_problem_test_rows", "ocffm_problem_save_binary", "ocffm_problem_load_binary",
     "ocffm_problem_recommend", "ocffm_problem_label_ranks", "ocffm_eval_from_ranks", "ocffm_problem_evaluate",
-    "ocffm_problem_score", "ocffm_problem_recommend_among",
+    "ocffm_problem_score", "ocffm_problem_recommend_among", "ocffm_problem_label_ranks_among",
+    "ocffm_problem_evaluate_among",
     "ocffm_problem_cg_log", "ocffm_problem_set_profiling", "ocffm_problem_set_profile_filter",
     "ocffm_problem_kernel_stats",
     "ocffm_problem_reset_stats", "ocffm_problem_alg_bytes", "ocffm_problem_counter", "ocffm_problem_sync",
@@ -94,6 +95,7 @@ EXPORTS = [
     "ocffm_sgd_average", "ocffm_sgd_phi", "ocffm_sgd_get", "ocffm_sgd_set_w", "ocffm_sgd_get_info",
     "ocffm_sgd_sync", "ocffm_sgd_destroy",
     "ocffm_sgd_recommend", "ocffm_sgd_label_ranks", "ocffm_sgd_evaluate", "ocffm_sgd_counter",
+    "ocffm_sgd_score", "ocffm_sgd_recommend_among", "ocffm_sgd_label_ranks_among", "ocffm_sgd_evaluate_among",
 ]
 
 _lib = None
@@ -143,6 +145,8 @@ def lib():
     L.ocffm_problem_recommend_among.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
     L.ocffm_eval_from_ranks.argtypes = [u64, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_problem_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_problem_label_ranks_among.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ocffm_problem_evaluate_among.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_problem_save_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_load_binary.argtypes = [vp, C.c_char_p]
     L.ocffm_problem_cg_log.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]
@@ -171,6 +175,10 @@ def lib():
     L.ocffm_sgd_label_ranks.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ocffm_sgd_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_sgd_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    L.ocffm_sgd_score.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.ocffm_sgd_recommend_among.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
+    L.ocffm_sgd_label_ranks_among.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ocffm_sgd_evaluate_among.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_sgd_destroy.restype = None
     _lib = L
     return L
@@ -183,6 +191,54 @@ def _check(st: int) -> None:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _lists(candidates, rows: int):
+    """``candidates=(cptr, ccol)`` as the C entries take it: ``rows + 1`` uint64
+    offsets into the uint32 entries (and a pointer for an empty ``ccol``)."""
+    cptr = np.ascontiguousarray(candidates[0], dtype=np.uint64).reshape(-1)
+    ccol = np.ascontiguousarray(candidates[1], dtype=np.uint32).reshape(-1)
+    if cptr.size != rows + 1 or int(cptr.max()) > ccol.size:
+        raise OcffmError(E_ARG, "candidates: cptr needs rows + 1 offsets into ccol")
+    return cptr, (ccol if ccol.size else np.zeros(1, dtype=np.uint32))
+
+
+def _label_ranks(fn, among, h, X, seen, candidates):
+    """label_ranks of a problem or a trainer (``fn``; ``among`` with candidates)."""
+    i = X.info
+    ranks = np.full(max(1, i["nnz_y"]), RANK_NONE, dtype=np.uint32)
+    scores = np.full(max(1, i["nnz_y"]), -np.inf, dtype=np.float64)
+    ncand = np.zeros(max(1, i["m"]), dtype=np.uint32)
+    sh = None if seen is None else seen.h
+    if candidates is None:
+        _check(fn(h, X.h, sh, _ptr(ranks), _ptr(scores), _ptr(ncand)))
+    else:
+        cptr, ccol = _lists(candidates, int(i["m"]))
+        _check(among(h, X.h, sh, _ptr(cptr), _ptr(ccol), _ptr(ranks), _ptr(scores), _ptr(ncand)))
+    return ranks[: i["nnz_y"]], scores[: i["nnz_y"]], ncand[: i["m"]]
+
+
+def _evaluate(fn, among, h, X, cuts, seen, candidates) -> dict:
+    c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+    e = _Eval()
+    sh = None if seen is None else seen.h
+    if candidates is None:
+        _check(fn(h, X.h, sh, _ptr(c), c.size, C.byref(e)))
+    else:
+        cptr, ccol = _lists(candidates, int(X.info["m"]))
+        _check(among(h, X.h, sh, _ptr(cptr), _ptr(ccol), _ptr(c), c.size, C.byref(e)))
+    return e.as_dict()
+
+
+def _score(fn, h, X, rows, items) -> np.ndarray:
+    r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    j = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1)
+    if r.size != j.size:
+        raise OcffmError(E_ARG, "score: rows and items differ in length")
+    out = np.full(max(1, r.size), -np.inf, dtype=np.float64)
+    pad = np.zeros(1, dtype=np.uint32)
+    _check(fn(h, X.h, r.size, _ptr(r if r.size else pad), _ptr(j if j.size else pad), _ptr(out)))
+    return out[: r.size]
 
 
 def device_count() -> int:
@@ -373,44 +429,55 @@ class SgdTrainer:
         _check(lib().ocffm_sgd_sync(self.h))
 
     def recommend(self, X: "ImpData", topn: int = 10, exclude_labels: bool = False, row0: int = 0,
-                  rows: Optional[int] = None):
+                  rows: Optional[int] = None, candidates=None):
         """Top-``topn`` items of rows [row0, row0 + rows) of ``X`` (default: to its
         end) under the current W (include/ocffm.h ocffm_sgd_recommend):
         ``(items uint32 [rows, topn], scores float64 [rows, topn])``, score
         descending, equal scores by ascending item; unfilled slots hold
-        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels."""
+        ``REC_NONE`` / ``-inf``.  ``exclude_labels`` drops each row's own labels.
+        With ``candidates=(cptr, ccol)`` each row is ranked among its own list
+        only (ocffm_sgd_recommend_among), as in ``ImpProblem.recommend``."""
         if rows is None:
             rows = max(0, int(X.info["m"]) - row0)
         shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
         items = np.full(shape, REC_NONE, dtype=np.uint32)
         scores = np.full(shape, -np.inf, dtype=np.float64)
         flags = REC_EXCLUDE_LABELS if exclude_labels else 0
-        _check(lib().ocffm_sgd_recommend(self.h, X.h, row0, rows, topn, flags, items.ctypes.data_as(C.c_void_p),
-                                         scores.ctypes.data_as(C.c_void_p)))
+        if candidates is None:
+            _check(lib().ocffm_sgd_recommend(self.h, X.h, row0, rows, topn, flags, items.ctypes.data_as(C.c_void_p),
+                                             scores.ctypes.data_as(C.c_void_p)))
+            return items, scores
+        cptr, ccol = _lists(candidates, rows)
+        _check(lib().ocffm_sgd_recommend_among(self.h, X.h, row0, rows, _ptr(cptr), _ptr(ccol), topn, flags,
+                                               items.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
         return items, scores
 
-    def label_ranks(self, X: "ImpData", seen: Optional["ImpData"] = None):
+    def score(self, X: "ImpData", rows, items) -> np.ndarray:
+        """Scores of the pairs (row ``rows[e]`` of ``X``, item ``items[e]``) under
+        the current W (include/ocffm.h ocffm_sgd_score): float64 [npairs], the
+        values ``recommend`` returns for those pairs bit for bit; ``-inf`` for an
+        item that is no candidate."""
+        return _score(lib().ocffm_sgd_score, self.h, X, rows, items)
+
+    def label_ranks(self, X: "ImpData", seen: Optional["ImpData"] = None, candidates=None):
         """Exact rank of every label of ``X`` among its row's candidates
         (include/ocffm.h ocffm_sgd_label_ranks): ``(ranks uint32 [nnz_y], scores
         float64 [nnz_y], ncand uint32 [m])`` in ``X.labels()`` order.  ``seen``
         (same row count) removes its rows' labels from the candidates; a label
-        that is no candidate has ``RANK_NONE`` / ``-inf``."""
-        i = X.info
-        ranks = np.full(max(1, i["nnz_y"]), RANK_NONE, dtype=np.uint32)
-        scores = np.full(max(1, i["nnz_y"]), -np.inf, dtype=np.float64)
-        ncand = np.zeros(max(1, i["m"]), dtype=np.uint32)
-        _check(lib().ocffm_sgd_label_ranks(self.h, X.h, None if seen is None else seen.h, _ptr(ranks), _ptr(scores),
-                                           _ptr(ncand)))
-        return ranks[: i["nnz_y"]], scores[: i["nnz_y"]], ncand[: i["m"]]
+        that is no candidate has ``RANK_NONE`` / ``-inf``.  With
+        ``candidates=(cptr, ccol)`` (one list per row of ``X``) each label is
+        ranked among its row's list and labels only
+        (ocffm_sgd_label_ranks_among)."""
+        L = lib()
+        return _label_ranks(L.ocffm_sgd_label_ranks, L.ocffm_sgd_label_ranks_among, self.h, X, seen, candidates)
 
-    def evaluate(self, X: "ImpData", cuts=(5, 10, 20, 40, 80), seen: Optional["ImpData"] = None) -> dict:
+    def evaluate(self, X: "ImpData", cuts=(5, 10, 20, 40, 80), seen: Optional["ImpData"] = None,
+                 candidates=None) -> dict:
         """Ranking metrics of the current W on the labelled rows ``X``
-        (include/ocffm.h ocffm_sgd_evaluate): the dict of
-        ``ImpProblem.evaluate``."""
-        c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
-        e = _Eval()
-        _check(lib().ocffm_sgd_evaluate(self.h, X.h, None if seen is None else seen.h, _ptr(c), c.size, C.byref(e)))
-        return e.as_dict()
+        (include/ocffm.h ocffm_sgd_evaluate; with ``candidates``
+        ocffm_sgd_evaluate_among): the dict of ``ImpProblem.evaluate``."""
+        L = lib()
+        return _evaluate(L.ocffm_sgd_evaluate, L.ocffm_sgd_evaluate_among, self.h, X, cuts, seen, candidates)
 
     def counter(self, name: str) -> int:
         """Serving counter (include/ocffm.h ocffm_sgd_counter)."""
@@ -530,13 +597,8 @@ class ImpProblem:
                                                  items.ctypes.data_as(C.c_void_p),
                                                  scores.ctypes.data_as(C.c_void_p)))
             return items, scores
-        cptr = np.ascontiguousarray(candidates[0], dtype=np.uint64).reshape(-1)
-        ccol = np.ascontiguousarray(candidates[1], dtype=np.uint32).reshape(-1)
-        if cptr.size != rows + 1 or int(cptr.max()) > ccol.size:
-            raise OcffmError(E_ARG, "candidates: cptr needs rows + 1 offsets into ccol")
-        pad = np.zeros(1, dtype=np.uint32)  # (a pointer for an empty ccol)
-        _check(lib().ocffm_problem_recommend_among(self.h, X.h, row0, rows, _ptr(cptr),
-                                                   _ptr(ccol if ccol.size else pad), topn, flags,
+        cptr, ccol = _lists(candidates, rows)
+        _check(lib().ocffm_problem_recommend_among(self.h, X.h, row0, rows, _ptr(cptr), _ptr(ccol), topn, flags,
                                                    items.ctypes.data_as(C.c_void_p),
                                                    scores.ctypes.data_as(C.c_void_p)))
         return items, scores
@@ -546,41 +608,32 @@ class ImpProblem:
         the current model (include/ocffm.h ocffm_problem_score): float64
         [npairs], the values ``recommend`` returns for those pairs bit for bit;
         ``-inf`` for an item that is no candidate of its row."""
-        r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        j = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1)
-        if r.size != j.size:
-            raise OcffmError(E_ARG, "score: rows and items differ in length")
-        out = np.full(max(1, r.size), -np.inf, dtype=np.float64)
-        pad = np.zeros(1, dtype=np.uint32)
-        _check(lib().ocffm_problem_score(self.h, X.h, r.size, _ptr(r if r.size else pad), _ptr(j if j.size else pad),
-                                         _ptr(out)))
-        return out[: r.size]
+        return _score(lib().ocffm_problem_score, self.h, X, rows, items)
 
-    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None):
+    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None, candidates=None):
         """Exact rank of every label of ``X`` among its row's candidates
         (include/ocffm.h ocffm_problem_label_ranks): ``(ranks uint32 [nnz_y],
         scores float64 [nnz_y], ncand uint32 [m])`` in ``X.labels()`` order.
         ``seen`` (same row count) removes its rows' labels from the candidates;
-        a label that is no candidate has ``RANK_NONE`` / ``-inf``."""
-        i = X.info
-        ranks = np.full(max(1, i["nnz_y"]), RANK_NONE, dtype=np.uint32)
-        scores = np.full(max(1, i["nnz_y"]), -np.inf, dtype=np.float64)
-        ncand = np.zeros(max(1, i["m"]), dtype=np.uint32)
-        _check(lib().ocffm_problem_label_ranks(self.h, X.h, None if seen is None else seen.h, _ptr(ranks),
-                                               _ptr(scores), _ptr(ncand)))
-        return ranks[: i["nnz_y"]], scores[: i["nnz_y"]], ncand[: i["m"]]
+        a label that is no candidate has ``RANK_NONE`` / ``-inf``.  With
+        ``candidates=(cptr, ccol)`` (one list per row of ``X``, as in
+        ``recommend``) each label is ranked among the distinct candidates of its
+        row's list united with the row's labels
+        (ocffm_problem_label_ranks_among): the sampled-negatives protocol."""
+        L = lib()
+        return _label_ranks(L.ocffm_problem_label_ranks, L.ocffm_problem_label_ranks_among, self.h, X, seen,
+                            candidates)
 
-    def evaluate(self, X: ImpData, cuts=(5, 10, 20, 40, 80), seen: Optional[ImpData] = None) -> dict:
+    def evaluate(self, X: ImpData, cuts=(5, 10, 20, 40, 80), seen: Optional[ImpData] = None,
+                 candidates=None) -> dict:
         """Ranking metrics of the current model on the labelled rows ``X``
-        (include/ocffm.h ocffm_problem_evaluate): a dict with ``rows``,
-        ``rows_used``, ``labels``, ``labels_ranked``, ``cuts``, ``loss``,
-        ``mrr``, ``auc`` and one array per cut for ``prec``, ``recall``,
-        ``ndcg``, ``map`` and ``hit``."""
-        c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
-        e = _Eval()
-        _check(lib().ocffm_problem_evaluate(self.h, X.h, None if seen is None else seen.h, _ptr(c), c.size,
-                                            C.byref(e)))
-        return e.as_dict()
+        (include/ocffm.h ocffm_problem_evaluate; with ``candidates``
+        ocffm_problem_evaluate_among): a dict with ``rows``, ``rows_used``,
+        ``labels``, ``labels_ranked``, ``cuts``, ``loss``, ``mrr``, ``auc`` and
+        one array per cut for ``prec``, ``recall``, ``ndcg``, ``map`` and
+        ``hit``."""
+        L = lib()
+        return _evaluate(L.ocffm_problem_evaluate, L.ocffm_problem_evaluate_among, self.h, X, cuts, seen, candidates)
 
     def save_binary(self, path: str) -> None:
         _check(lib().ocffm_problem_save_binary(self.h, path.encode()))
