@@ -645,6 +645,113 @@ int ocffm_sgd_evaluate_among(ocffm_sgd *s, const ocffm_data *X, const ocffm_data
 int ocffm_sgd_counter(ocffm_sgd *s, const char *name, int64_t *value);
 void ocffm_sgd_destroy(ocffm_sgd *s);
 
+/* ------------------------------------------------------- saved models
+ * Serving from a saved model (no reference counterpart: the reference writes
+ * its model files and reads none).  An ocffm_model holds, on one device, the
+ * field space (f, fu, fv, k, Ds), W and H of every used block padded as the
+ * problem pads them, the current item catalogue in the serving sweeps' form
+ * (the item-side cross tables Q_c, n x kp, and b_j) and an optional popularity
+ * vector.  It holds no training rows.  Single GPU only: a model is neither
+ * sharded nor replicated; one host thread drives it. */
+typedef struct ocffm_model ocffm_model;
+
+typedef struct ocffm_model_info {
+  uint32_t f, fu, fv, k, kp; /* fields (all, user, item); latent dimension and its padded length */
+  uint32_t nblocks, nused;   /* f (f + 1) / 2 field-pair blocks; those with tables                */
+  int32_t self_side;         /* 1: the side blocks are used (0: a model trained with --ns)        */
+  int32_t precision, device; /* of a model; 0 and -1 from ocffm_model_file_info                   */
+  int32_t has_items;         /* a catalogue is set                                                */
+  uint64_t n, npop;          /* catalogue items; popularity entries                               */
+  /* in: NULL, or room for ds_cap / used_cap values; out: Ds of the f fields
+   * (user fields first) and one flag per block b12 = index_vec(f1, f2, f). */
+  uint64_t *Ds;
+  uint8_t *used;
+  uint32_t ds_cap, used_cap;
+} ocffm_model_info;
+
+/* Reads and fully validates a model file on the host; no device is touched.
+ * binary == 0: the text model ocffm_problem_save_model writes (header lines
+ * f, fu, fv, k, then the Ds; table lines "W|H,f1,f2,row v1 ... vk", blocks in
+ * (f1, f2) order, W before H, rows in order).  binary != 0: the layout
+ * documented at ocffm_problem_save_binary.  The side blocks are either all
+ * present or all absent (--ns: unused blocks).
+ * OCFFM_E_IO for a path that cannot be read.  OCFFM_E_DATA for a text file
+ * with an absent cross block, a block with only one of W / H, a missing,
+ * repeated or out-of-order row, a wrong value count, a non-numeric token or
+ * trailing text; for a binary file that is truncated, has a wrong block
+ * index or table size, or trailing bytes; for either with f != fu + fv,
+ * k outside 1..128 or only some of the side blocks. */
+int ocffm_model_file_info(const char *path, int binary, ocffm_model_info *out);
+
+/* A model from a file (the checks of ocffm_model_file_info; a bad file leaves
+ * no object behind), with its tables in `precision` (OCFFM_FP64 / OCFFM_FP32)
+ * on `device`.  The text model holds six significant digits per value. */
+int ocffm_model_load_text(const char *path, int precision, int device, ocffm_model **out);
+int ocffm_model_load_binary(const char *path, int precision, int device, ocffm_model **out);
+/* A model from a problem's current state, copied device to device: W / H, and
+ * as its catalogue the problem's resident item side (Q and b, which training
+ * updates incrementally) and its popularity, so that every serving result on
+ * the training catalogue has the problem's own bits.  Precision and device are
+ * the problem's.  OCFFM_E_STATE before init / load_binary; OCFFM_E_ARG for a
+ * sharded problem. */
+int ocffm_model_from_problem(ocffm_problem *p, ocffm_model **out);
+
+/* Replaces the catalogue by the rows of V, any item rows in the model's item
+ * field space: read them with the model's item Ds (ocffm_model_get_ds, the
+ * last fv values), as a test file is read with the train Ds.  The rows are
+ * laid out per field and projected on the device through W / H (Q_c[j] and
+ * b_j in the arithmetic of the problem's own projection, bit for bit).  The
+ * popularity is cleared.  V.m == 0 gives an empty catalogue: every serving
+ * call then returns OCFFM_REC_NONE / -inf / OCFFM_RANK_NONE.
+ * OCFFM_E_ARG for more fields than fv; OCFFM_E_DATA for a node with
+ * idx >= Ds[fid].  The counter "project_us" holds the projection's time. */
+int ocffm_model_set_items(ocffm_model *m, const ocffm_data *V);
+/* The cold rows' scores: pop[j] for the catalogue items j < min(npop, n); the
+ * indices are catalogue indices (rows of the last ocffm_model_set_items), not
+ * the labels of any training set.  Without it (npop == 0 clears it) a cold
+ * row, one with no kept feature node, has no candidates.  OCFFM_E_STATE
+ * before ocffm_model_set_items; OCFFM_E_ARG for a NULL pop with npop > 0. */
+int ocffm_model_set_popularity(ocffm_model *m, const double *pop, uint64_t npop);
+
+/* Serving: the signatures, order, exclusion, short-row, duplicate and
+ * reproducibility rules (OCFFM_REC_ROWS, OCFFM_REC_SLICES, OCFFM_REC_SEG, read
+ * when the model is created) and the error codes of the ocffm_problem_ entry
+ * of the same name, on the model's catalogue: n is its item count, npop the
+ * popularity entries, X rows in the model's user field space (read with the
+ * first fu values of ocffm_model_get_ds).  OCFFM_E_STATE before
+ * ocffm_model_set_items (a model from a problem has a catalogue).  The query
+ * rows are projected by one launch per call (the kernel family of
+ * ocffm_model_set_items).  Counters (ocffm_model_counter; an unknown name reads
+ * 0): "rec_setup_us" / "eval_setup_us", the last call's host set-up as for the
+ * problem; "project_us", the last ocffm_model_set_items' projection;
+ * "rank_kernel_us", the last call's serving launches between HIP events. */
+int ocffm_model_recommend(ocffm_model *m, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
+                          uint32_t flags, uint32_t *items, double *scores);
+int ocffm_model_score(ocffm_model *m, const ocffm_data *X, uint64_t npairs, const uint32_t *prow,
+                      const uint32_t *pitem, double *out);
+int ocffm_model_recommend_among(ocffm_model *m, const ocffm_data *X, uint64_t row0, uint64_t rows,
+                                const uint64_t *cptr, const uint32_t *ccol, uint32_t topn, uint32_t flags,
+                                uint32_t *items, double *scores);
+int ocffm_model_label_ranks(ocffm_model *m, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
+                            double *scores, uint32_t *ncand);
+int ocffm_model_label_ranks_among(ocffm_model *m, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                                  const uint32_t *ccol, uint32_t *ranks, double *scores, uint32_t *ncand);
+int ocffm_model_evaluate(ocffm_model *m, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
+                         uint32_t ncut, ocffm_eval *out);
+int ocffm_model_evaluate_among(ocffm_model *m, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
+                               const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out);
+int ocffm_model_counter(ocffm_model *m, const char *name, int64_t *value);
+
+/* Access.  ocffm_model_get_info fills Ds / used when the caller gave room;
+ * ocffm_model_get_ds writes the f field sizes (user fields first).
+ * ocffm_model_get copies to the host as fp64 like ocffm_problem_get: what 'W',
+ * 'H' (block b12), 'Q' (the catalogue's cross table of cross block b12,
+ * n x k), 'b' (b_j, n values). */
+int ocffm_model_get_info(ocffm_model *m, ocffm_model_info *out);
+int ocffm_model_get_ds(ocffm_model *m, uint64_t *out);
+int ocffm_model_get(ocffm_model *m, char what, uint32_t b12, double *out, uint64_t cap, uint64_t *len);
+void ocffm_model_destroy(ocffm_model *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // common.hpp — host-side pieces shared by the library's translation units
-// (solver.hip: the Newton-CG path; sgd.hip: the SGD/AdaGrad path): error
+// (solver.hip: the Newton-CG path; sgd.hip: the SGD/AdaGrad path; model.hip:
+// the stand-alone model handle): error
 // codes through the C ABI, HIP/RCCL checks, device buffers.
 #pragma once
 

@@ -1,0 +1,118 @@
+// predict.cpp — serve from a saved model (no reference counterpart: the
+// reference writes its model files and reads none).
+//
+//   predict [options] model_file item_file
+//   --fp32 / --fp64 (default fp64), --device N;
+//   --binary: model_file is the snapshot of train --binary-out (default: the
+//   text model of train -o, six digits per value);
+//   --popularity <train_file>: the cold rows' scores, count / total of every
+//   label of this labelled file (ffm.cpp:143,172-176); its labels are indices
+//   into item_file, so this is for the training catalogue;
+//   the serving options of train (serve_cli.hpp), with the same meaning and
+//   the same output bytes: --recommend / --topn / --rec-out / --rec-unseen /
+//   --rec-candidates, --eval / --eval-cuts / --eval-seen / --eval-candidates.
+// item_file is the catalogue: any item rows in the model's item field space
+// (read with the model's item Ds, as a test file is with the train Ds).
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/ocffm.h"
+#include "serve_cli.hpp"
+
+static std::string usage() {
+  return "usage: predict [options] model_file item_feature_file\n"
+         "\n"
+         "options:\n"
+         "--fp32 | --fp64: device arithmetic (default fp64)\n"
+         "--device <n>: HIP device ordinal\n"
+         "--binary: model_file is a binary snapshot (train --binary-out); default: the text model (train -o)\n"
+         "--popularity <path>: labelled train file whose label counts score the rows without features\n" +
+         serve_usage("");
+}
+
+int main(int argc, char **argv) {
+  int precision = OCFFM_FP64, device = 0;
+  bool binary = false;
+  std::string pop_path;
+  ServeOptions so;
+  try {
+    if (argc == 1) throw std::invalid_argument(usage());
+    int i = 1;
+    for (; i < argc; i++) {
+      const std::string a = argv[i];
+      auto value = [&](bool numeric, const char *msg) -> const char * {
+        if (i + 1 >= argc) throw std::invalid_argument(msg);
+        i++;
+        if (numeric && !is_numerical(argv[i])) throw std::invalid_argument(a + " should be followed by a number");
+        return argv[i];
+      };
+      if (a == "--fp32") precision = OCFFM_FP32;
+      else if (a == "--fp64") precision = OCFFM_FP64;
+      else if (a == "--device") device = std::atoi(value(true, "need a device ordinal after --device"));
+      else if (a == "--binary") binary = true;
+      else if (a == "--popularity") pop_path = value(false, "need to specify path after --popularity");
+      else if (so.take(a, value)) continue;
+      else break;
+    }
+    so.validate();
+    if (i + 1 >= argc) throw std::invalid_argument("model file and item file not specified");
+    if (i + 2 < argc) throw std::invalid_argument(std::string("unexpected argument: ") + argv[i + 2]);
+    const std::string model_path = argv[i], item_path = argv[i + 1];
+
+    const bool timing = std::getenv("OCFFM_TIMING") != nullptr;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto phase = [&](const char *name) {
+      const auto t = std::chrono::steady_clock::now();
+      if (timing) std::fprintf(stderr, "[timing] %-8s %9.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
+      t_prev = t;
+    };
+    // the model file is read and checked on the host before any device work
+    ocffm_model_info mi{};
+    check(ocffm_model_file_info(model_path.c_str(), binary ? 1 : 0, &mi));
+    std::vector<std::uint64_t> ds(mi.f);
+    mi.Ds = ds.data();
+    mi.ds_cap = mi.f;
+    check(ocffm_model_file_info(model_path.c_str(), binary ? 1 : 0, &mi));
+    ocffm_data *V = nullptr, *Up = nullptr;
+    check(ocffm_data_read(item_path.c_str(), 0, ds.data() + mi.fu, mi.fv, &V));
+    std::vector<double> pop;
+    if (!pop_path.empty()) {
+      check(ocffm_data_read(pop_path.c_str(), 1, nullptr, 0, &Up));
+      ocffm_data_info ui;
+      check(ocffm_data_get_info(Up, &ui));
+      std::vector<std::uint64_t> yptr(ui.m + 1), ycol(ui.nnz_y + 1);
+      check(ocffm_data_get_labels(Up, yptr.data(), ycol.data()));
+      pop.assign(ui.n, 0.0);
+      for (std::uint64_t p = 0; p < ui.nnz_y; p++) pop[ycol[p]] += 1;
+      double s = 0;
+      for (double v : pop) s += v;
+      for (double &v : pop) v /= s;
+      ocffm_data_free(Up);
+    }
+    ServeLists lists;
+    lists.read(so, ds.data(), mi.fu);
+    phase("read");
+    ocffm_model *mod = nullptr;
+    check(binary ? ocffm_model_load_binary(model_path.c_str(), precision, device, &mod)
+                 : ocffm_model_load_text(model_path.c_str(), precision, device, &mod));
+    phase("load");
+    check(ocffm_model_set_items(mod, V));
+    if (!pop.empty()) check(ocffm_model_set_popularity(mod, pop.data(), pop.size()));
+    phase("items");
+    serve(ModelServer{mod}, so, lists, ds.data(), mi.fu, phase);
+    ocffm_model_destroy(mod);
+    ocffm_data_free(V);
+  } catch (std::invalid_argument &e) {
+    std::cerr << e.what() << std::endl;
+    return 1;
+  } catch (Fail &e) {
+    std::cerr << "error: " << e.what() << std::endl;
+    return e.code == OCFFM_E_ARG ? 1 : 2;
+  }
+  return 0;
+}

@@ -37,6 +37,7 @@
 #include "devbuild.h"
 #include "host_data.h"
 #include "kernels.hpp"
+#include "model_source.hpp"
 #include "rank_driver.hpp"
 
 namespace ocffm {
@@ -341,6 +342,7 @@ struct ProblemBase {
   virtual void save_binary(const std::string &path) = 0;
   virtual void load_binary(const std::string &path) = 0;
   virtual void sync() = 0;
+  virtual void model_source(ModelSource &out) = 0;
   virtual std::vector<std::pair<std::string, uint64_t>> layout_digest() = 0;
   virtual bool has_test() const = 0;
   virtual uint32_t nr_pass() const = 0;
@@ -1212,6 +1214,39 @@ template <typename real> class Problem final : public ProblemBase {
   }
 
   // ----------------------------------------------------------- access
+  // The current tables for a stand-alone model (model_source.hpp): W / H, the
+  // resident item side and the popularity, as the serving calls see them.
+  void model_source(ModelSource &o) override {
+    need_init();
+    if (comm_.active()) throw Error(OCFFM_E_ARG, "a model is taken from a single-GPU problem");
+    sync_owned();
+    sync();
+    o.precision = std::is_same<real, double>::value ? OCFFM_FP64 : OCFFM_FP32;
+    o.device = prm_.device;
+    o.f = f_;
+    o.fu = fu_;
+    o.fv = fv_;
+    o.k = k_;
+    o.kp = kp_;
+    o.Ds = U_.Ds;
+    o.Ds.insert(o.Ds.end(), V_.Ds.begin(), V_.Ds.end());
+    o.used.assign(blocks_.size(), 0);
+    o.W.assign(blocks_.size(), nullptr);
+    o.H.assign(blocks_.size(), nullptr);
+    for (size_t b = 0; b < blocks_.size(); b++)
+      if (blocks_[b].used) {
+        o.used[b] = 1;
+        o.W[b] = W_[b].p;
+        o.H[b] = H_[b].p;
+      }
+    o.Q.clear();
+    for (uint32_t f1 = 0; f1 < fu_; f1++)
+      for (uint32_t f2 = fu_; f2 < f_; f2++) o.Q.push_back(Q_[block_index(f1, f2, f_)].p);
+    o.b = V_.bias.p;
+    o.n = n_;
+    o.popular = popular_.p;
+    o.npop = std::min<uint64_t>(npop_, n_);
+  }
   uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) override {
     need_init();
     const real *src = nullptr;
@@ -4206,6 +4241,11 @@ using namespace ocffm;
 struct ocffm_problem {
   std::unique_ptr<ProblemBase> p;
 };
+
+void ocffm::problem_model_source(ocffm_problem *prob, ModelSource &out) {
+  if (!prob || !prob->p) throw Error(OCFFM_E_ARG, "null problem");
+  prob->p->model_source(out);
+}
 
 extern "C" {
 

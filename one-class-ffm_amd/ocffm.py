@@ -73,6 +73,14 @@ class _KStat(C.Structure):
                 ("alg_bytes", C.c_double), ("alg_flops", C.c_double)]
 
 
+class _ModelInfo(C.Structure):
+    _fields_ = [("f", C.c_uint32), ("fu", C.c_uint32), ("fv", C.c_uint32), ("k", C.c_uint32), ("kp", C.c_uint32),
+                ("nblocks", C.c_uint32), ("nused", C.c_uint32), ("self_side", C.c_int32),
+                ("precision", C.c_int32), ("device", C.c_int32), ("has_items", C.c_int32),
+                ("n", C.c_uint64), ("npop", C.c_uint64), ("Ds", C.c_void_p), ("used", C.c_void_p),
+                ("ds_cap", C.c_uint32), ("used_cap", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p)
 
 EXPORTS = [
@@ -96,6 +104,11 @@ EXPORTS = [
     "ocffm_sgd_sync", "ocffm_sgd_destroy",
     "ocffm_sgd_recommend", "ocffm_sgd_label_ranks", "ocffm_sgd_evaluate", "ocffm_sgd_counter",
     "ocffm_sgd_score", "ocffm_sgd_recommend_among", "ocffm_sgd_label_ranks_among", "ocffm_sgd_evaluate_among",
+    "ocffm_model_file_info", "ocffm_model_load_text", "ocffm_model_load_binary", "ocffm_model_from_problem",
+    "ocffm_model_set_items", "ocffm_model_set_popularity", "ocffm_model_recommend", "ocffm_model_score",
+    "ocffm_model_recommend_among", "ocffm_model_label_ranks", "ocffm_model_label_ranks_among",
+    "ocffm_model_evaluate", "ocffm_model_evaluate_among", "ocffm_model_counter", "ocffm_model_get_info",
+    "ocffm_model_get_ds", "ocffm_model_get", "ocffm_model_destroy",
 ]
 
 _lib = None
@@ -180,6 +193,25 @@ def lib():
     L.ocffm_sgd_label_ranks_among.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.ocffm_sgd_evaluate_among.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
     L.ocffm_sgd_destroy.restype = None
+    L.ocffm_model_file_info.argtypes = [C.c_char_p, i32, C.POINTER(_ModelInfo)]
+    L.ocffm_model_load_text.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.ocffm_model_load_binary.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.ocffm_model_from_problem.argtypes = [vp, C.POINTER(vp)]
+    L.ocffm_model_set_items.argtypes = [vp, vp]
+    L.ocffm_model_set_popularity.argtypes = [vp, vp, u64]
+    L.ocffm_model_recommend.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp]
+    L.ocffm_model_score.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.ocffm_model_recommend_among.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
+    L.ocffm_model_label_ranks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ocffm_model_label_ranks_among.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ocffm_model_evaluate.argtypes = [vp, vp, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_model_evaluate_among.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_model_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    L.ocffm_model_get_info.argtypes = [vp, C.POINTER(_ModelInfo)]
+    L.ocffm_model_get_ds.argtypes = [vp, vp]
+    L.ocffm_model_get.argtypes = [vp, C.c_char, u32, vp, u64, C.POINTER(u64)]
+    L.ocffm_model_destroy.argtypes = [vp]
+    L.ocffm_model_destroy.restype = None
     _lib = L
     return L
 
@@ -715,6 +747,154 @@ class ImpProblem:
         _check(lib().ocffm_problem_layout_digest(self.h, names, dig, n.value, C.byref(n)))
         raw = names.raw
         return {raw[48 * i:48 * (i + 1)].split(b"\0", 1)[0].decode(): int(dig[i]) for i in range(n.value)}
+
+
+def _model_info(fill) -> dict:
+    """Two calls of an info entry (``fill(info) -> status``): the sizes, then
+    Ds and the used-block flags."""
+    i = _ModelInfo()
+    _check(fill(i))
+    ds = np.zeros(max(1, i.f), dtype=np.uint64)
+    used = np.zeros(max(1, i.nblocks), dtype=np.uint8)
+    i.Ds, i.used, i.ds_cap, i.used_cap = ds.ctypes.data, used.ctypes.data, ds.size, used.size
+    _check(fill(i))
+    return dict(f=int(i.f), fu=int(i.fu), fv=int(i.fv), k=int(i.k), kp=int(i.kp), nblocks=int(i.nblocks),
+                nused=int(i.nused), self_side=bool(i.self_side), precision=int(i.precision), device=int(i.device),
+                has_items=bool(i.has_items), n=int(i.n), npop=int(i.npop), Ds=ds[: i.f].copy(),
+                used=used[: i.nblocks].astype(bool))
+
+
+def model_file_info(path: str, binary: bool = False) -> dict:
+    """Read and fully validate a saved model on the host (include/ocffm.h
+    ocffm_model_file_info; no GPU): ``f``, ``fu``, ``fv``, ``k``, ``kp``, ``Ds``
+    and the ``used`` flag of every block.  A malformed file raises
+    ``OcffmError`` with ``E_DATA``, a missing one with ``E_IO``."""
+    return _model_info(lambda i: lib().ocffm_model_file_info(path.encode(), int(binary), C.byref(i)))
+
+
+class Model:
+    """A stand-alone model handle (include/ocffm.h ocffm_model): W / H of a
+    saved or trained model and an item catalogue, on one GPU, with the serving
+    calls of ``ImpProblem`` and no training rows."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    @classmethod
+    def load_text(cls, path: str, precision: int = FP64, device: int = 0) -> "Model":
+        """The text model ``ImpProblem.save_model`` writes (six digits per value)."""
+        h = C.c_void_p()
+        _check(lib().ocffm_model_load_text(path.encode(), precision, device, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def load_binary(cls, path: str, precision: int = FP64, device: int = 0) -> "Model":
+        """The snapshot ``ImpProblem.save_binary`` writes."""
+        h = C.c_void_p()
+        _check(lib().ocffm_model_load_binary(path.encode(), precision, device, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_problem(cls, g: "ImpProblem") -> "Model":
+        """The problem's current W / H with its item side and popularity as the
+        catalogue, copied device to device: results on the training catalogue
+        are the problem's own bits."""
+        h = C.c_void_p()
+        _check(lib().ocffm_model_from_problem(g.h, C.byref(h)))
+        return cls(h)
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.ocffm_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def info(self) -> dict:
+        return _model_info(lambda i: lib().ocffm_model_get_info(self.h, C.byref(i)))
+
+    @property
+    def Ds(self) -> np.ndarray:
+        """The f field sizes, user fields first."""
+        out = np.zeros(max(1, self.info["f"]), dtype=np.uint64)
+        _check(lib().ocffm_model_get_ds(self.h, _ptr(out)))
+        return out[: self.info["f"]]
+
+    @property
+    def item_Ds(self) -> np.ndarray:
+        """The item fields' sizes: read an item file with these before ``set_items``."""
+        return self.Ds[self.info["fu"]:]
+
+    def set_items(self, V: ImpData) -> None:
+        """Replace the catalogue by the item rows ``V`` (include/ocffm.h
+        ocffm_model_set_items); clears the popularity."""
+        _check(lib().ocffm_model_set_items(self.h, V.h))
+
+    def set_popularity(self, pop) -> None:
+        """Cold rows' scores over the catalogue items ``j < len(pop)`` (catalogue
+        indices); an empty ``pop`` clears them."""
+        a = np.ascontiguousarray(pop, dtype=np.float64).reshape(-1)
+        _check(lib().ocffm_model_set_popularity(self.h, _ptr(a) if a.size else None, a.size))
+
+    def get(self, what: str, b12: int = 0) -> np.ndarray:
+        """``'W'`` / ``'H'`` of block ``b12``, ``'Q'`` (the catalogue's cross table
+        of cross block ``b12``) or ``'b'``, as float64."""
+        n = C.c_uint64(0)
+        _check(lib().ocffm_model_get(self.h, what.encode(), b12, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.float64)
+        _check(lib().ocffm_model_get(self.h, what.encode(), b12, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def recommend(self, X: ImpData, topn: int = 10, exclude_labels: bool = False, row0: int = 0,
+                  rows: Optional[int] = None, candidates=None):
+        """Top-``topn`` catalogue items of rows [row0, row0 + rows) of ``X``
+        (include/ocffm.h ocffm_model_recommend): the shape, order and rules of
+        ``ImpProblem.recommend``; with ``candidates=(cptr, ccol)`` each row is
+        ranked among its own list (ocffm_model_recommend_among)."""
+        if rows is None:
+            rows = max(0, int(X.info["m"]) - row0)
+        shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
+        items = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        flags = REC_EXCLUDE_LABELS if exclude_labels else 0
+        if candidates is None:
+            _check(lib().ocffm_model_recommend(self.h, X.h, row0, rows, topn, flags, items.ctypes.data_as(C.c_void_p),
+                                               scores.ctypes.data_as(C.c_void_p)))
+            return items, scores
+        cptr, ccol = _lists(candidates, rows)
+        _check(lib().ocffm_model_recommend_among(self.h, X.h, row0, rows, _ptr(cptr), _ptr(ccol), topn, flags,
+                                                 items.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
+        return items, scores
+
+    def score(self, X: ImpData, rows, items) -> np.ndarray:
+        """Scores of the pairs (row ``rows[e]`` of ``X``, catalogue item
+        ``items[e]``) (include/ocffm.h ocffm_model_score): float64 [npairs], the
+        values ``recommend`` returns bit for bit; ``-inf`` for no candidate."""
+        return _score(lib().ocffm_model_score, self.h, X, rows, items)
+
+    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None, candidates=None):
+        """Exact rank of every label of ``X`` among its row's candidates
+        (include/ocffm.h ocffm_model_label_ranks; with ``candidates``
+        ocffm_model_label_ranks_among): ``(ranks, scores, ncand)`` as
+        ``ImpProblem.label_ranks``; labels are catalogue indices."""
+        L = lib()
+        return _label_ranks(L.ocffm_model_label_ranks, L.ocffm_model_label_ranks_among, self.h, X, seen, candidates)
+
+    def evaluate(self, X: ImpData, cuts=(5, 10, 20, 40, 80), seen: Optional[ImpData] = None,
+                 candidates=None) -> dict:
+        """Ranking metrics on the labelled rows ``X`` (include/ocffm.h
+        ocffm_model_evaluate; with ``candidates`` ocffm_model_evaluate_among):
+        the dict of ``ImpProblem.evaluate``."""
+        L = lib()
+        return _evaluate(L.ocffm_model_evaluate, L.ocffm_model_evaluate_among, self.h, X, cuts, seen, candidates)
+
+    def counter(self, name: str) -> int:
+        """Serving counter (include/ocffm.h ocffm_model_counter)."""
+        v = C.c_int64(0)
+        _check(lib().ocffm_model_counter(self.h, name.encode(), C.byref(v)))
+        return v.value
 
 
 def eval_from_ranks(yptr, ranks, ncand, scores=None, cuts=(5, 10, 20, 40, 80)) -> dict:
