@@ -460,7 +460,10 @@ int ocffm_problem_alg_bytes(ocffm_problem *p, double *bytes);
  * "ccg_halves" (cross halves solved on per-column Grams), "hot_halves"
  * (cross halves whose steps read hot rows' Grams), "capped_launches"
  * (launches whose grid a residency or *_BLOCKS cap cut below its work, so
- * that its blocks loop).  An unknown name reads 0. */
+ * that its blocks loop), "pcol_gd" / "pcol_hs" (cross gradient / Hessian-
+ * vector row passes that gathered a partner field's own table through
+ * partner columns, OCFFM_PCOL) and "pcol_bytes" (bytes of those column
+ * arrays).  An unknown name reads 0. */
 int ocffm_problem_counter(ocffm_problem *p, const char *name, int64_t *value);
 int ocffm_problem_sync(ocffm_problem *p);
 /* Digests (FNV-1a over the bytes) of every array of the device data layout

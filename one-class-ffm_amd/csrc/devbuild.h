@@ -71,8 +71,9 @@ class Builder {
   void csc(const CSR &x, uint64_t D, int nsg, const uint8_t *own, CSC &out);
 
   // one: every row has exactly one node; idlike: additionally D == R and
-  // every column holds exactly one row (solver.hip DevField).
-  void flags(const CSR &x, const CSC &c, uint64_t D, bool &one, bool &idlike);
+  // every column holds exactly one row; unit: every value is exactly 1
+  // (solver.hip DevField).
+  void flags(const CSR &x, const CSC &c, uint64_t D, bool &one, bool &idlike, bool &unit);
 
   // One node per row: per-column sum of x^2 in the order of xsq_col (fp64,
   // no FMA); max(D, 1) values in the builder's scratch.

@@ -140,12 +140,14 @@ __global__ void k_job_pad(uint64_t b, uint64_t e, Job *__restrict__ jobs) {
 
 // -------------------------------------------------------- flags / sums
 __global__ void k_flags(uint64_t R, const int64_t *__restrict__ xptr, uint64_t D, const int64_t *__restrict__ cptr,
-                        unsigned long long *__restrict__ bad) {
-  unsigned long long br = 0, bc = 0;
+                        uint64_t nnz, const double *__restrict__ xval, unsigned long long *__restrict__ bad) {
+  unsigned long long br = 0, bc = 0, bv = 0;
   GSTRIDE(i, R) br += xptr[i + 1] - xptr[i] != 1;
   GSTRIDE(d, D) bc += cptr[d + 1] - cptr[d] != 1;
+  GSTRIDE(p, nnz) bv += xval[p] != 1.0;
   if (br) atomicAdd(&bad[0], br);
   if (bc) atomicAdd(&bad[1], bc);
+  if (bv) atomicAdd(&bad[2], bv);
 }
 
 // Sum of x^2 per column (one block per column) in the order xsq_col
@@ -494,15 +496,17 @@ void Builder::csc(const CSR &x, uint64_t D, int nsg, const uint8_t *own, CSC &ou
   if (pad > nlight) hipLaunchKernelGGL(k_job_pad, grid(pad - nlight), TB, 0, s_, nlight, pad, out.jobs.p);
 }
 
-void Builder::flags(const CSR &x, const CSC &c, uint64_t D, bool &one, bool &idlike) {
-  unsigned long long *bad = (unsigned long long *)grow(t_bad_, 2);
-  HIPCHK(hipMemsetAsync(bad, 0, 2 * sizeof(int64_t), s_));
-  hipLaunchKernelGGL(k_flags, grid(std::max(x.R, D)), TB, 0, s_, x.R, x.xptr.p, D, c.cptr, bad);
-  unsigned long long h[2];
+void Builder::flags(const CSR &x, const CSC &c, uint64_t D, bool &one, bool &idlike, bool &unit) {
+  unsigned long long *bad = (unsigned long long *)grow(t_bad_, 3);
+  HIPCHK(hipMemsetAsync(bad, 0, 3 * sizeof(int64_t), s_));
+  hipLaunchKernelGGL(k_flags, grid(std::max(std::max(x.R, D), x.nnz)), TB, 0, s_, x.R, x.xptr.p, D, c.cptr, x.nnz,
+                     x.xval.p, bad);
+  unsigned long long h[3];
   HIPCHK(hipMemcpyAsync(h, bad, sizeof(h), hipMemcpyDeviceToHost, s_));
   sync();
   one = x.R > 0 && x.nnz == x.R && h[0] == 0;
   idlike = one && D == x.R && h[1] == 0;
+  unit = x.nnz > 0 && h[2] == 0;
 }
 
 const double *Builder::xsq(const CSC &c, uint64_t D) {

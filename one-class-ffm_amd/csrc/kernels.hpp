@@ -1123,7 +1123,13 @@ template <typename real, int KP> struct TMma {
   }
 };
 
-template <typename real, int KP, bool MLDS, int BM, bool TP = false, bool PRB = false>
+// XC (BM_ENTER): the previous block's partner rows dxs are gathered through
+// their own per-position columns xcol into a table of xrows rows (a one-hot
+// unit-valued partner field's own table, solver.hip partner_cols); else
+// through ycol like q_j (xrows = q1rows).  The same substitution for q_j needs
+// no code: the host passes the field's columns, table and row count as ycol,
+// Q1 and q1rows (passes that gather the partner bias b1[j] keep the projection).
+template <typename real, int KP, bool MLDS, int BM, bool TP = false, bool PRB = false, bool XC = false>
 __global__ __launch_bounds__(BLOCK, sizeof(real) == 8 ? OCFFM_GD_OCC64 : (BM == BM_ENTER ? OCFFM_GD_OCC : OCFFM_GD_OCC_IN)) void k_gd_cross_seg(uint64_t nseg, const Seg *__restrict__ segs,
                                                         const uint32_t *__restrict__ ycol,
                                                         real *__restrict__ yt, const real *__restrict__ Q1,
@@ -1137,15 +1143,17 @@ __global__ __launch_bounds__(BLOCK, sizeof(real) == 8 ? OCFFM_GD_OCC64 : (BM == 
                                                         const uint32_t *__restrict__ perm,
                                                         const real *__restrict__ Tpre,
                                                         const real *__restrict__ ytv,
-                                                        const uint32_t *__restrict__ sord) {
+                                                        const uint32_t *__restrict__ sord,
+                                                        const uint32_t *__restrict__ xcol, uint64_t xrows) {
   using G = Geo<real, KP>;
   using PP = PosPass<real, KP, sizeof(real) == 8 ? OCFFM_GD_GB64 : (BM == BM_ENTER ? OCFFM_GD_GB : OCFFM_GD_GB_IN)>;
+  static_assert(!XC || BM == BM_ENTER, "xcol: the entering pass");
   // TP: T_i precomputed by k_rows_T (one row load; no M in LDS)
   // ytv (BM_IN): the stored value is read from the other orientation through
   // perm (ytv[perm[q]]), so the entering pass of the block needs no refresh
   // of this orientation (solver.hip gradient)
   const BufView qb = buf_view(Q1, q1rows * KP * sizeof(real)), bb = buf_view(b1, q1rows * sizeof(real));
-  const BufView xb = buf_view(dxs, dxs ? q1rows * KP * sizeof(real) : 0);
+  const BufView xb = buf_view(dxs, dxs ? xrows * KP * sizeof(real) : 0);
   extern __shared__ __align__(16) unsigned char smem_raw[];
   real *Ms = reinterpret_cast<real *>(smem_raw);
   const real *Mp = M;
@@ -1202,6 +1210,8 @@ __global__ __launch_bounds__(BLOCK, sizeof(real) == 8 ? OCFFM_GD_OCC64 : (BM == 
       uint32_t jj[PP::UT];
       real yv[PP::UT];
       PP::load_cols(ycol, p0, sgm.e, li, jj);
+      uint32_t jx[XC ? PP::UT : 1];  // XC: the positions' rows of dxs
+      if constexpr (XC) PP::load_cols(xcol, p0, sgm.e, li, jx);
 #pragma unroll
       for (int t = 0; t < PP::UT; t++) {
         const int64_t q = p0 + li + t * G::LPR;
@@ -1221,7 +1231,9 @@ __global__ __launch_bounds__(BLOCK, sizeof(real) == 8 ? OCFFM_GD_OCC64 : (BM == 
           yb[u] = PP::template at<bt + u>(yv, li);
           qv[u] = bld<real>(qb, PP::row_off(j, qb, li));
           if (gbias) yb[u] += ai + bld1<real>(bb, j == POS_NONE ? bb.oob : j * (uint32_t)sizeof(real));
-          if constexpr (WR) {
+          if constexpr (XC) {
+            xv[u] = bld<real>(xb, PP::row_off(PP::template at<bt + u>(jx, li), xb, li));
+          } else if constexpr (WR) {
             if (dxs) xv[u] = bld<real>(xb, PP::row_off(j, xb, li));
           }
         });

@@ -64,6 +64,15 @@ template <typename real> __global__ void k_to_real(uint64_t n, const double *__r
     out[i] = (real)in[i];
 }
 
+// Per-position partner columns of a one-node-per-row partner field:
+// pcol[q] = xidx[ycol[q]], the field's column of position q's partner row
+// (Problem::partner_cols).
+static __global__ void k_partner_cols(uint64_t npos, const uint32_t *__restrict__ ycol,
+                                      const uint32_t *__restrict__ xidx, uint32_t *__restrict__ pcol) {
+  for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < npos; q += (uint64_t)gridDim.x * blockDim.x)
+    pcol[q] = xidx[ycol[q]];
+}
+
 // -------------------------------------------------------------- profiling
 struct KStat {
   uint64_t launches = 0;
@@ -112,6 +121,14 @@ template <typename real> struct DevField {
   DevBuf<unsigned> cnt;  // per-column arrival tickets (zero at rest)
   bool idlike = false;   // one node per row and each feature in exactly one row (CSC = identity)
   bool one = false;      // exactly one node per row (xptr[i] == i)
+  bool unit = false;     // every value is exactly 1
+  // Partner columns (one && unit && !idlike, few columns): the
+  // field's column of every positive's partner row, in the other side's
+  // position order, through which that side's cross row passes gather this
+  // field's own table instead of its projection.  Built on the first half
+  // that uses it (partner_cols); pcol_state: 0 not decided, 1 built, -1 no.
+  DevBuf<uint32_t> pcol;
+  int pcol_state = 0;
   // Per-column Grams (kernels.hpp k_col_gram / k_hv_cgram) of a one-node-per-row
   // field with few columns: chunk jobs over the CSC and the D x k x k Grams.
   // Allocated on the first Gram half (col_grams); gpart holds the ordered
@@ -594,7 +611,7 @@ template <typename real> class Problem final : public ProblemBase {
         const std::string f = p + ".F" + std::to_string(fi) + ".";
         num(f + "D", F.D);
         num(f + "nnz", F.nnz);
-        num(f + "flags", (F.one ? 1 : 0) | (F.idlike ? 2 : 0) | (F.excl ? 4 : 0));
+        num(f + "flags", (F.one ? 1 : 0) | (F.idlike ? 2 : 0) | (F.excl ? 4 : 0) | (F.unit ? 8 : 0));
         num(f + "njw", F.njw);
         num(f + "nslot", F.nslot);
         num(f + "snjw", F.snjw);
@@ -1497,7 +1514,7 @@ template <typename real> class Problem final : public ProblemBase {
       if (owned && fi < d.f) ownership(*F, who[fi]);
       dev::CSC c;
       B.csc(x, F->D, nsg(), F->excl ? F->own.p : nullptr, c);
-      B.flags(x, c, F->D, F->one, F->idlike);
+      B.flags(x, c, F->D, F->one, F->idlike, F->unit);
       F->xptr = std::move(x.xptr);
       F->xidx = std::move(x.xidx);
       to_real_dev(x.xval.p, x.nnz, F->xval);
@@ -1551,6 +1568,8 @@ template <typename real> class Problem final : public ProblemBase {
       F->nnz = xidx.size();
       F->one = R > 0 && F->nnz == R;
       for (uint64_t i = 0; i < R && F->one; i++) F->one = xptr[i + 1] - xptr[i] == 1;
+      F->unit = F->nnz > 0;
+      for (size_t p = 0; p < xval.size() && F->unit; p++) F->unit = xval[p] == 1.0;
       if (F->nnz == R && F->D == R && R > 0) {
         std::vector<uint8_t> seen(F->D, 0);
         bool ok = true;
@@ -2228,10 +2247,12 @@ template <typename real> class Problem final : public ProblemBase {
         // block-excluded base: enter this block (store), or read it inside
         const real *cur = nullptr, *drow = nullptr, *dxs = nullptr;
         bool enter = false;
+        uint32_t bprev = h.b12;  // the block left by an entering pass
         if (lazy_ok_) {
           cur = h.P1;
           enter = !(excl_.on && excl_.b12 == h.b12);
           if (enter && excl_.on) {  // leave the previous block in the same pass
+            bprev = excl_.b12;
             drow = h.user ? P_[excl_.b12].p : Q_[excl_.b12].p;  // indexed by this half's rows
             dxs = h.user ? Q_[excl_.b12].p : P_[excl_.b12].p;   // indexed by the partner
           }
@@ -2240,6 +2261,38 @@ template <typename real> class Problem final : public ProblemBase {
         // cur / drow are rows of the C tables already counted; entering stores e
         // and gathers the previous block's partner rows
         if (enter) bytes += (double)own.npos * rs + (dxs ? (double)ps.R * KP * rs : 0);
+        // Partner columns (partner_cols): q_j from the partner field's own
+        // table, and dxs_j from the previous block's, each where its field is
+        // eligible.  A pass that also gathers the partner bias b1[j] (the
+        // full base, or the first entering pass) needs ycol for it and keeps
+        // the projection for q_j.
+        const uint32_t *qcol = own.ycol.p, *xcol = nullptr;
+        const real *q1 = h.Q1;
+        uint64_t q1rows = ps.R, xrows = ps.R;
+        const real *const dxs0 = dxs;  // (the projection: the probe build's gathers)
+        if (cur && !(enter && !dxs)) {
+          DevField<real> &Fo = partner_field(h.b12, h.user);
+          if (const uint32_t *pc = partner_cols(own, ps, Fo)) {
+            qcol = pc;
+            q1 = h.user ? H_[h.b12].p : W_[h.b12].p;
+            q1rows = Fo.D;
+            bytes -= (double)(ps.R - Fo.D) * KP * rs;
+          }
+        }
+        if (dxs) {
+          DevField<real> &Fx = partner_field(bprev, h.user);
+          if (const uint32_t *pc = partner_cols(own, ps, Fx)) {
+            xcol = pc;
+            dxs = h.user ? H_[bprev].p : W_[bprev].p;
+            xrows = Fx.D;
+            bytes += (double)own.npos * 4 - (double)(ps.R - Fx.D) * KP * rs;  // (its own column array)
+          }
+        }
+        if (qcol != own.ycol.p || xcol) counters["pcol_gd"]++;
+        if (dxs && !xcol && qcol != own.ycol.p) {  // q_j through its columns: dxs_j keeps the partner rows
+          xcol = own.ycol.p;
+          bytes += (double)own.npos * 4;
+        }
         // inside the block (BM_IN): read the stored value through perm from
         // the orientation the entering pass wrote (no refresh in between)
         const bool via = ytvia_ && cur && !enter && !side_pending_;
@@ -2268,14 +2321,19 @@ template <typename real> class Problem final : public ProblemBase {
             // one resident wave of blocks (OCFFM_GD_FILL): the grid-stride
             // loop then has no partial last wave of blocks
             const size_t gsm = TP ? 0 : (ML ? msz + (TM ? TMma<real, KP>::tile_bytes() : 0) : 0);
-            unsigned grid = grid_for(own.nseg, 4 * Gm::NSG, gd_blocks_);
-            if (gd_fill_) grid = std::min(grid, resident(k_gd_cross_seg<real, KP, ML, BM, TP>, gsm));
-            capped(blocks_of(own.nseg, 4 * Gm::NSG), grid);
-            launch(k_gd_cross_seg<real, KP, ML, BM, TP>, grid, BLOCK, gsm, own.nseg, own.segs.p, own.ycol.p, own.yt.p, h.Q1, (int)C_,
-                (const real *const *)(tabs_.p + (h.user ? 0 : C_)), M_.p, sums_.p, own.bias.p, h.partner->bias.p, w_,
-                r_, h_.p, (uint64_t)h.partner->R, cur, drow, dxs, (const uint32_t *)own.perm.p,
-                TP ? (const real *)Tpre_.p : (const real *)nullptr,
-                via ? (const real *)h.partner->yt.p : (const real *)nullptr, sord(own));
+            auto go4 = [&](auto xcc) {  // XC: dxs through its own columns (entering passes)
+              constexpr bool XC = decltype(xcc)::value && BM == BM_ENTER;
+              unsigned grid = grid_for(own.nseg, 4 * Gm::NSG, gd_blocks_);
+              if (gd_fill_) grid = std::min(grid, resident(k_gd_cross_seg<real, KP, ML, BM, TP, false, XC>, gsm));
+              capped(blocks_of(own.nseg, 4 * Gm::NSG), grid);
+              launch(k_gd_cross_seg<real, KP, ML, BM, TP, false, XC>, grid, BLOCK, gsm, own.nseg, own.segs.p, qcol, own.yt.p, q1, (int)C_,
+                  (const real *const *)(tabs_.p + (h.user ? 0 : C_)), M_.p, sums_.p, own.bias.p, h.partner->bias.p, w_,
+                  r_, h_.p, q1rows, cur, drow, dxs, (const uint32_t *)own.perm.p,
+                  TP ? (const real *)Tpre_.p : (const real *)nullptr,
+                  via ? (const real *)h.partner->yt.p : (const real *)nullptr, sord(own), xcol, xrows);
+            };
+            if (xcol) go4(std::true_type());
+            else go4(std::false_type());
           };
           if constexpr (std::is_same<real, float>::value && (KP == 32 || KP == 64) && !ML) {
             if (tp) {
@@ -2297,8 +2355,10 @@ template <typename real> class Problem final : public ProblemBase {
             launch(k_gd_cross_seg<real, KP, false, BM, false, true>, grid_for(own.nseg, 4 * Gm::NSG, gd_blocks_), BLOCK,
                    0, own.nseg, own.segs.p, own.ycol.p, own.yt.p, h.Q1, (int)C_,
                    (const real *const *)(tabs_.p + (h.user ? 0 : C_)), M_.p, sums_.p, own.bias.p, h.partner->bias.p, w_,
-                   r_, h_.p, (uint64_t)h.partner->R, cur, drow, dxs, (const uint32_t *)own.perm.p,
-                   (const real *)nullptr, via ? (const real *)h.partner->yt.p : (const real *)nullptr, sord(own));
+                   r_, h_.p, (uint64_t)h.partner->R, cur, drow, dxs0,
+                   (const uint32_t *)own.perm.p, (const real *)nullptr,
+                   via ? (const real *)h.partner->yt.p : (const real *)nullptr, sord(own), (const uint32_t *)nullptr,
+                   (uint64_t)h.partner->R);
           };
           prof_launch("gd_probe", bytes, [&] {
             if (!cur) probe(std::integral_constant<int, BM_FULL>());
@@ -3624,6 +3684,48 @@ template <typename real> class Problem final : public ProblemBase {
     sd.sord.upload(ord);
   }
 
+  // Partner columns.  A partner field F that is one node per
+  // row with value 1 and not id-like has P[i] == W[xidx[i]] element for
+  // element after every kernel that writes either (k_utx forms 0 + 1 W, the
+  // updates P + 1 s and W + s from the same s), so a cross row pass may
+  // gather row xidx[j] of the block's own D x k table in place of row j of
+  // the R x k projection: the same values in the same order, from a table
+  // that stays in L2 (or L1).  Taken where 2 D <= R (a table at least half
+  // the projection has little cache share to win and still costs the array)
+  // on one rank (the owned-field and item-owned paths keep tables that are
+  // whole only after sync_owned).  pcol: 4 B per positive of `own` and
+  // eligible field, built by one gather on the first half that uses it; if
+  // its allocation fails the passes stay on the projection.
+  // OCFFM_PCOL=0: off.
+  bool pcol_on_ = !std::getenv("OCFFM_PCOL") || std::atoi(std::getenv("OCFFM_PCOL")) != 0;
+  const uint32_t *partner_cols(DevSide<real> &own, DevSide<real> &ps, DevField<real> &F) {
+    if (F.pcol_state == 0) {
+      F.pcol_state = -1;
+      if (pcol_on_ && !comm_.active() && F.one && F.unit && !F.idlike && !F.excl && 2 * F.D <= ps.R && own.npos > 0) {
+        uint32_t *p = nullptr;
+        if (hipMalloc((void **)&p, own.npos * sizeof(uint32_t)) == hipSuccess) {
+          F.pcol.p = p;
+          F.pcol.n = own.npos;
+          prof_launch("partner_cols", (double)own.npos * 12, [&] {
+            launch(k_partner_cols, grid_for(own.npos, BLOCK, 2048), BLOCK, 0, (uint64_t)own.npos,
+                   (const uint32_t *)own.ycol.p, (const uint32_t *)F.xidx.p, p);
+          });
+          F.pcol_state = 1;
+          counters["pcol_bytes"] += (int64_t)F.pcol.bytes();
+        } else {
+          (void)hipGetLastError();  // out of memory: the projection serves
+        }
+      }
+    }
+    return F.pcol_state == 1 ? F.pcol.p : nullptr;
+  }
+  // the partner field of a cross block's half on side `user` (its table: H_ or W_ of the block)
+  DevField<real> &partner_field(uint32_t b12, bool user) {
+    const Block &b = blocks_[b12];
+    const uint32_t fo = user ? b.f2 : b.f1;
+    return *side(fo).F[fidx(fo)];
+  }
+
   // Segment length profile of a side (host, once): short_segs when at
   // least 99 % of its segments hold at most 16 positives (outbrain's users:
   // ~1 positive per row), where k_hs_cross_seg's passes of 16 positions
@@ -3742,8 +3844,19 @@ template <typename real> class Problem final : public ProblemBase {
           const size_t qsz = (size_t)KP * KP * sizeof(real);
           const bool lds = qsz <= 32 * 1024;
           const size_t smem = lds ? qsz : 0;
+          // partner columns (partner_cols): q_j from the partner field's own table
+          const uint32_t *qcol = own.ycol.p;
+          const real *q1 = h.Q1;
+          uint64_t q1rows = h.partner->R;
+          DevField<real> &Fo = partner_field(h.b12, h.user);
+          if (const uint32_t *pc = partner_cols(own, *h.partner, Fo)) {
+            qcol = pc;
+            q1 = h.user ? H_[h.b12].p : W_[h.b12].p;
+            q1rows = Fo.D;
+            counters["pcol_hs"]++;
+          }
           const double bytes = (double)own.R * 16 + (double)F.nnz * (4 + rs) + (double)F.D * KP * rs +
-                               (double)own.npos * 4 + (double)h.partner->R * KP * rs + (double)own.R * KP * rs;
+                               (double)own.npos * 4 + (double)q1rows * KP * rs + (double)own.R * KP * rs;
           // tau on the matrix cores (kernels.hpp TauTile) where the rows take
           // it per row: fp32, QTQ in LDS, no column tau, no hot rows, segment order
           const bool tt = tau_mfma_ && TauTile<real, KP>::OK && lds && !coltau(h) && !hot(h) && !sord(own);
@@ -3759,8 +3872,8 @@ template <typename real> class Problem final : public ProblemBase {
                 if (row_fill_) grid = std::min(grid, resident(k_hs_cross_seg<real, KP, ML, PW, TT>, sm));
                 capped(blocks_of(own.nseg, TT ? TauTile<real, KP>::SB : 4 * Gm::NSG), grid);
                 launch(k_hs_cross_seg<real, KP, ML, PW, TT>, grid, BLOCK, sm,
-                       own.nseg, own.segs.p, F.xptr.p, F.xidx.p, F.xval.p, Vd_.p, own.ycol.p, h.Q1,
-                       (uint64_t)h.partner->R, coltau(h) ? (const real *)nullptr : (const real *)qtq_, w_, h_.p, run,
+                       own.nseg, own.segs.p, F.xptr.p, F.xidx.p, F.xval.p, Vd_.p, qcol, q1,
+                       q1rows, coltau(h) ? (const real *)nullptr : (const real *)qtq_, w_, h_.p, run,
                        Rv_.p, Hv_.p, st_.p, it, F.segd.p, F.segx.p,
                        hot(h) ? (const uint32_t *)own.hot_seg.p : (const uint32_t *)nullptr, (const real *)hotG_.p,
                        sord(own));
