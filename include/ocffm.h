@@ -150,6 +150,62 @@ int ocffm_problem_cache_sasb(ocffm_problem *p);
  * stdout table every 10th epoch when a test set is present. */
 int ocffm_problem_solve(ocffm_problem *p);
 
+/* The training objective (the reference's func(), ffm.cpp:1321-1351, which
+ * its train never calls), in closed form from the state resident on the
+ * device; no m x n pass.  With yhat_ij = a_i + b_j + sum_c <P_c[i], Q_c[j]>:
+ *   value  = 0.5 (pos + omega (all - on_pos) + reg)
+ *   pos    = sum over the label entries (i,j) of the training rows of
+ *            (1 - yhat_ij)^2 (an entry listed twice counts twice)
+ *   on_pos = the same sum of (r - yhat_ij)^2
+ *   all    = sum_{i<m} sum_{j<n} (r - yhat_ij)^2
+ *   reg    = sum over W and H of the used blocks of lambda_d |row_d|^2
+ * lambda_d = lambda, or under freq lambda times the frequency of feature d
+ * in the row's own field (W of block (f1,f2): field f1; H: field f2).
+ * func() ignores freq while the gradient and CG use it (ffm.cpp:561-570):
+ * under freq the value is the function the solver descends, not func()'s.
+ *  - Arithmetic: every sum across row ranges, blocks and tiles is fp64 in a
+ *    fixed order (no floating-point atomics): two calls on the same state
+ *    return equal bits.  An OCFFM_FP32 problem accumulates at most 1024 rows
+ *    of a Gram tile in fp32 before widening.  OCFFM_OBJ_BLOCKS /
+ *    OCFFM_OBJ_GROUP (read at create) change the value by fp64 reassociation
+ *    only.
+ *  - Does not change the solver state (tables, projections, y~, biases, the
+ *    CG log).
+ *  - Sharded problems: collective; every rank returns the global value (m,
+ *    labels: global counts).
+ *  - Errors: OCFFM_E_ARG for a NULL problem or out; OCFFM_E_STATE before
+ *    init / load_binary.
+ * The launches are the kernel family "objective" of the statistics below;
+ * the counter "obj_us" holds the last call's wall time. */
+typedef struct ocffm_objective {
+  double value, pos, on_pos, all, reg;
+  uint64_t m, n, labels; /* global rows, item rows, label entries */
+} ocffm_objective;
+int ocffm_problem_objective(ocffm_problem *p, ocffm_objective *out);
+
+/* ocffm_problem_solve with the objective reported and, optionally, a stop on
+ * its relative decrease.  With o == NULL or objective_every == 0 and
+ * tol <= 0 it is ocffm_problem_solve, byte for byte on stdout.  Otherwise
+ * rank 0 prints one line per evaluation,
+ *   objective iter=<init|epoch> value=<%.17g> decrease=<%.6g>
+ * (decrease: (F_prev - F) / |F_prev|, absent on the init line), after that
+ * epoch's validation row if there is one.  On an early stop with a test set
+ * the last epoch is validated and its row printed unless it already was.
+ * rep (may be NULL): epochs run, whether the tolerance stopped the solve, the
+ * objective at init and at the last evaluation (0 when never evaluated). */
+typedef struct ocffm_solve_opts {
+  uint32_t objective_every; /* 0: never; e: before the first epoch and after every e-th */
+  double tol;               /* <= 0: none; else stop after epoch t when (F_prev - F_t) <= tol |F_prev|,
+                               F_prev the previous evaluation (F_0 at init); implies objective_every >= 1 */
+  uint32_t min_pass;        /* never stop before this many epochs */
+} ocffm_solve_opts;
+typedef struct ocffm_solve_report {
+  uint32_t epochs;
+  int32_t converged;
+  double objective0, objective;
+} ocffm_solve_report;
+int ocffm_problem_solve_ex(ocffm_problem *p, const ocffm_solve_opts *o, ocffm_solve_report *rep);
+
 /* ImpProblem::validate (ffm.cpp:925-1016): loss = sqrt(ploss/m_te), p@k and
  * nDCG@k at k = 5,10,20,40,80. */
 typedef struct ocffm_metrics {
@@ -463,7 +519,8 @@ int ocffm_problem_alg_bytes(ocffm_problem *p, double *bytes);
  * that its blocks loop), "pcol_gd" / "pcol_hs" (cross gradient / Hessian-
  * vector row passes that gathered a partner field's own table through
  * partner columns, OCFFM_PCOL) and "pcol_bytes" (bytes of those column
- * arrays).  An unknown name reads 0. */
+ * arrays), "obj_us" (wall time of the last ocffm_problem_objective call, in
+ * microseconds).  An unknown name reads 0. */
 int ocffm_problem_counter(ocffm_problem *p, const char *name, int64_t *value);
 int ocffm_problem_sync(ocffm_problem *p);
 /* Digests (FNV-1a over the bytes) of every array of the device data layout

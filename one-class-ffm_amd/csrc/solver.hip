@@ -38,6 +38,7 @@
 #include "host_data.h"
 #include "kernels.hpp"
 #include "model_source.hpp"
+#include "obj_kernels.hpp"
 #include "rank_driver.hpp"
 
 namespace ocffm {
@@ -338,6 +339,7 @@ struct ProblemBase {
   virtual void one_epoch() = 0;
   virtual void solve_block(uint32_t f1, uint32_t f2) = 0;
   virtual void cache_sasb() = 0;
+  virtual void objective(ocffm_objective *out) = 0;
   virtual void validate(ocffm_metrics *m, bool forced = false, double *per_row_ndcg = nullptr, uint64_t cap = 0) = 0;
   virtual uint64_t test_rows() const = 0;
   virtual void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags,
@@ -404,6 +406,9 @@ template <typename real> class Problem final : public ProblemBase {
       if (j >= V.m) throw Error(OCFFM_E_DATA, "train label >= number of item rows (reference: out-of-bounds read)");
     m_glob_ = U.m;
     n_ = V.m;
+    labels_glob_ = U.ycol.size();
+    if (const char *e = std::getenv("OCFFM_OBJ_BLOCKS")) obj_blocks_ = (uint64_t)std::max(1, std::atoi(e));
+    if (const char *e = std::getenv("OCFFM_OBJ_GROUP")) obj_group_ = (uint32_t)std::max(1, std::atoi(e));
     if (const char *e = std::getenv("OCFFM_SEG_LEN")) seg_len_ = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("OCFFM_LOOKAHEAD")) lookahead_ = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("OCFFM_HS_BLOCKS")) hs_blocks_ = (unsigned)std::max(1, std::atoi(e));
@@ -948,6 +953,124 @@ template <typename real> class Problem final : public ProblemBase {
         });
       });
     }
+  }
+
+  // ---------------------------------------------------------- objective
+  // The training objective in closed form (obj_kernels.hpp) from
+  // the resident state: a pair-Gram pass and an aggregate pass per side, the
+  // Frobenius reduction, one pass over the user-major positives and one over
+  // W / H.  Reads only: P/Q/y~, the biases, cg_log and the speculative-update
+  // predictions are untouched (flush_base restores the full base only when an
+  // interrupted epoch left the block-excluded form on).  Sharded: every
+  // user-side term is a sum over this rank's rows and the Frobenius product
+  // is linear in G_U, so seven scalars are all-reduced; the item side (whole
+  // Q_c and b on every rank) and reg (whole tables after sync_owned) are not.
+  static constexpr uint64_t OBJ_PART_BYTES = 256ull << 20;  // cap of the row ranges' tile partials
+  void objective(ocffm_objective *out) override {
+    need_init();
+    const auto t0 = std::chrono::steady_clock::now();
+    flush_base();
+    sync_owned();
+    const uint32_t C = C_, ntp = C * (C + 1) / 2;
+    const uint64_t D = (uint64_t)C * kp_, gsz = std::max<uint64_t>(1, (uint64_t)ntp * kp_ * kp_), nvec = 2 * D + 2;
+    // tables per group and group pairs (grid.y); row ranges (grid.x): at least 32 rows each, by default
+    // four blocks per CU over the whole grid, never more partials than OBJ_PART_BYTES
+    const uint32_t G = std::min(obj_group_, std::max(C, 1u)), ng = (C + G - 1) / G, ngp = ng * (ng + 1) / 2;
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1, OBJ_PART_BYTES / (gsz * 8)),
+                                            obj_blocks_ ? obj_blocks_ : std::max(1u, 4 * ncu_ / std::max(ngp, 1u)));
+    auto ranges = [&](uint64_t R) { return std::clamp<uint64_t>((R + 31) / 32, 1, cap); };
+    const uint64_t need = std::max(ranges(U_.R), ranges(V_.R)) * std::max(gsz, nvec);
+    if (objpart_.n < need) objpart_.alloc(need, false);
+    if (objG_[0].n != gsz)
+      for (int sd = 0; sd < 2; sd++) {
+        objG_[sd].alloc(gsz);
+        objvec_[sd].alloc(nvec);
+      }
+    if (!objs_.p) objs_.alloc(16);
+    const double rs = sizeof(real);
+    for (int sd = 0; sd < 2; sd++) {
+      DevSide<real> &s = sd ? V_ : U_;
+      const uint64_t nbx = ranges(s.R), rpb = std::max<uint64_t>(1, (s.R + nbx - 1) / nbx);
+      const real *const *tabs = (const real *const *)(tabs_.p + (sd ? C_ : 0));
+      if (nbx < (s.R + 31) / 32 && obj_blocks_) n_capped++;
+      with_kp(kp_, [&](auto K) {
+        constexpr int KP = decltype(K)::value;
+        if (C > 0) {
+          const dim3 grid((unsigned)nbx, ngp);
+          const unsigned threads = 64u * std::min<uint32_t>(BLOCK / 64, G * G);
+          const double flops = 2.0 * (double)s.R * (double)gsz;
+          prof_launch("objective", (double)s.R * D * rs + (double)nbx * gsz * 8, [&] {
+            if constexpr (obj_mfma_kp<real, KP>()) {
+              if (!no_mfma_) {
+                launch(k_obj_gram<real, KP, true>, grid, threads, 0, (uint64_t)s.R, C, tabs, objpart_.p, rpb, G, ng);
+                return;
+              }
+            }
+            launch(k_obj_gram<real, KP, false>, grid, threads, 0, (uint64_t)s.R, C, tabs, objpart_.p, rpb, G, ng);
+          }, flops);
+          prof_launch("objective", (double)(nbx + 1) * gsz * 8, [&] {
+            launch(k_reduce_parts<double, double>, (unsigned)((gsz + 15) / 16), BLOCK, 0, nbx, gsz, (uint64_t)0, gsz,
+                   (const double *)objpart_.p, (uint64_t)0, (double *)nullptr, objG_[sd].p);
+          });
+        }
+        prof_launch("objective", (double)s.R * (D + 1) * rs + (double)nbx * nvec * 8, [&] {
+          launch(k_obj_vecs<real, KP>, (unsigned)nbx, BLOCK, 0, (uint64_t)s.R, (int)C, tabs, (const real *)s.bias.p,
+                 sd ? 0.0 : -r_, objpart_.p, rpb);
+        });
+        prof_launch("objective", (double)(nbx + 1) * nvec * 8, [&] {
+          launch(k_reduce_parts<double, double>, (unsigned)((nvec + 15) / 16), BLOCK, 0, nbx, nvec, (uint64_t)0, nvec,
+                 (const double *)objpart_.p, (uint64_t)0, (double *)nullptr, objvec_[sd].p);
+        });
+      });
+    }
+    prof_launch("objective", 2.0 * gsz * 8 + 2.0 * nvec * 8, [&] {
+      launch(k_obj_frob, std::clamp<unsigned>(ntp, 1, 1024), BLOCK, 0, C, kp_, (const double *)objG_[0].p,
+             (const double *)objG_[1].p, (const double *)objvec_[0].p, (const double *)objvec_[1].p, part_.p, tick_.p,
+             objs_.p);
+    });
+    prof_launch("objective", (double)U_.npos * (4 + rs) + (double)(U_.R + V_.R) * rs, [&] {
+      launch(k_obj_pos<real>, grid_for(U_.npos, 4 * BLOCK, 1024), BLOCK, 0, (uint64_t)U_.npos, (uint64_t)U_.R,
+             (const int64_t *)U_.yptr.p, (const uint32_t *)U_.ycol.p, (const real *)U_.yt.p, (const real *)U_.bias.p,
+             (const real *)V_.bias.p, 1.0 - r_, part_.p, tick_.p, objs_.p + 5);
+    });
+    // W and H of every used block; under --freq each row weighs its own field's frequency
+    std::vector<ObjTab<real>> tl;
+    uint64_t nel = 0;
+    for (size_t b12 = 0; b12 < blocks_.size(); b12++) {
+      if (!blocks_[b12].used) continue;
+      for (int t = 0; t < 2; t++) {
+        const uint32_t fl = t == 0 ? blocks_[b12].f1 : blocks_[b12].f2;
+        DevField<real> &F = *side(fl).F[fidx(fl)];
+        tl.push_back(ObjTab<real>{t == 0 ? W_[b12].p : H_[b12].p, prm_.freq ? F.freqw.p : nullptr, F.D * kp_});
+        nel += F.D * kp_;
+      }
+    }
+    if (objtabs_.n != tl.size()) objtabs_.alloc(tl.size(), false);
+    if (!tl.empty()) HIPCHK(hipMemcpy(objtabs_.p, tl.data(), tl.size() * sizeof(tl[0]), hipMemcpyHostToDevice));
+    uint32_t lg = 0;
+    while ((1u << lg) < kp_) lg++;
+    prof_launch("objective", (double)nel * rs, [&] {
+      launch(k_obj_reg<real>, grid_for(nel, 8 * BLOCK, 1024), BLOCK, 0, (uint32_t)tl.size(),
+             (const ObjTab<real> *)objtabs_.p, lg, part_.p, tick_.p, objs_.p + 9);
+    });
+    // [0] <G_U, G_V>  [1] u_alpha.v_1  [2] u_1.v_b  [3] sum alpha  [4] sum alpha^2  [5] pos  [6] on_pos:
+    // sums over this rank's user rows; [7] sum b  [8] sum b^2  [9] sum fw x^2: whole on every rank
+    allreduce_dev_d(objs_.p, 7);
+    double h[10];
+    HIPCHK(hipMemcpyAsync(h, objs_.p, sizeof(h), hipMemcpyDeviceToHost, stream_));
+    sync();
+    const double m = (double)m_glob_, n = (double)n_;
+    out->pos = h[5];
+    out->on_pos = h[6];
+    out->all = h[0] + 2 * h[1] + 2 * h[2] + n * h[4] + m * h[8] + 2 * h[3] * h[7];
+    out->reg = lam_ * h[9];
+    out->value = 0.5 * (out->pos + w_ * (out->all - out->on_pos) + out->reg);
+    out->m = m_glob_;
+    out->n = n_;
+    out->labels = labels_glob_;
+    flush_prof();
+    counters["obj_us"] = std::max<int64_t>(
+        1, std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   }
 
   // ------------------------------------------------------- validation
@@ -4165,6 +4288,13 @@ template <typename real> class Problem final : public ProblemBase {
   uint32_t k_, kp_, fu_, fv_, f_, C_ = 0;
   double w_, lam_, r_;
   uint64_t m_glob_ = 0, n_ = 0, u0_ = 0, u1_ = 0, dmax_ = 0, npop_ = 0;
+  // objective(): OCFFM_OBJ_BLOCKS (cap on the Gram pass's row ranges; 0: the scratch cap alone) and
+  // OCFFM_OBJ_GROUP (tables per group), the row ranges' partials, the two sides' tiles and O(D)
+  // aggregates, the scalar results and the W / H table list of the regulariser pass
+  uint64_t labels_glob_ = 0, obj_blocks_ = 0;
+  uint32_t obj_group_ = 2;
+  DevBuf<double> objpart_, objG_[2], objvec_[2], objs_;
+  DevBuf<ObjTab<real>> objtabs_;
   // positives per segment: fp64 48 (8.99 -> 8.89 ms per kkbox epoch at the
   // 10-epoch command: fewer segments for the feature passes to sum), fp32 32
   // (48: within noise; 64: slower gradient passes)
@@ -4745,6 +4875,66 @@ int ocffm_problem_solve(ocffm_problem *prob) {
         if (talk) ocffm_print_epoch(&m, it);
       }
     }
+  });
+}
+
+int ocffm_problem_objective(ocffm_problem *prob, ocffm_objective *out) {
+  PROB_CALL({
+    if (!out) throw Error(OCFFM_E_ARG, "null argument");
+    prob->p->objective(out);
+  });
+}
+
+// solve with the objective evaluated every o->objective_every epochs and the
+// relative-decrease stop; without either it is ocffm_problem_solve.
+int ocffm_problem_solve_ex(ocffm_problem *prob, const ocffm_solve_opts *o, ocffm_solve_report *rep) {
+  uint32_t every = o ? o->objective_every : 0;
+  const double tol = o ? o->tol : 0.0;
+  if (tol > 0 && every == 0) every = 1;
+  if (every == 0) {
+    const int st = ocffm_problem_solve(prob);
+    if (st == OCFFM_OK && rep) *rep = ocffm_solve_report{prob->p->nr_pass(), 0, 0.0, 0.0};
+    return st;
+  }
+  return guarded([&] {
+    if (!prob || !prob->p) throw Error(OCFFM_E_ARG, "null problem");
+    ProblemBase &P = *prob->p;
+    const bool talk = P.rank() == 0;
+    auto line = [&](const char *iter, double v, const double *dec) {
+      char buf[160];
+      if (dec) std::snprintf(buf, sizeof(buf), "objective iter=%s value=%.17g decrease=%.6g", iter, v, *dec);
+      else std::snprintf(buf, sizeof(buf), "objective iter=%s value=%.17g", iter, v);
+      if (talk) std::cout << buf << std::endl;
+    };
+    if (P.has_test() && talk) ocffm_print_header();
+    ocffm_objective ob;
+    P.objective(&ob);
+    ocffm_solve_report r{0, 0, ob.value, ob.value};
+    line("init", ob.value, nullptr);
+    double prev = ob.value;
+    for (uint32_t it = 0; it < P.nr_pass() && !r.converged; it++) {
+      P.one_epoch();
+      r.epochs = it + 1;
+      bool row = false;
+      ocffm_metrics m;
+      if (P.has_test() && it % 10 == 9) {
+        P.validate(&m);
+        if (talk) ocffm_print_epoch(&m, it);
+        row = true;
+      }
+      if ((it + 1) % every != 0) continue;
+      P.objective(&ob);
+      r.objective = ob.value;
+      const double dec = (prev - ob.value) / std::fabs(prev);  // relative to the previous evaluation
+      line(std::to_string(it + 1).c_str(), ob.value, &dec);
+      r.converged = tol > 0 && it + 1 >= o->min_pass && prev - ob.value <= tol * std::fabs(prev);
+      prev = ob.value;
+      if (r.converged && P.has_test() && !row) {  // the early stop's epoch is validated like a 10th one
+        P.validate(&m);
+        if (talk) ocffm_print_epoch(&m, it);
+      }
+    }
+    if (rep) *rep = r;
   });
 }
 

@@ -8,6 +8,11 @@
 // Build-only options (the reference would take them for the item file):
 //   --fp32 / --fp64 (default fp64, the reference's arithmetic type),
 //   --device N;
+//   --objective [every]: print the training objective before the first epoch
+//   and after every `every`-th (default 1), one `objective` line each;
+//   --tol <x>: stop after the epoch whose relative decrease of the objective
+//   is at most x (implies --objective); without either flag the solve and
+//   its output are the reference's;
 //   --binary-out <path>: after the solve, the binary snapshot
 //   (ocffm_problem_save_binary) that predict --binary serves from: the text
 //   model of -o holds six digits per value;
@@ -53,6 +58,8 @@ static std::string usage() {
          "--freq: enable freq-aware lambda\n"
          "--fp32 | --fp64: device arithmetic (default fp64)\n"
          "--device <n>: HIP device ordinal\n"
+         "--objective [every]: print the training objective at init and after every <every>-th iteration (default 1)\n"
+         "--tol <x>: stop once an iteration lowers the objective by at most x relative to the previous evaluation\n"
          "--binary-out <path>: after training, write the binary snapshot (ocffm_problem_save_binary) predict reads\n" +
          serve_usage("after training, ");
 }
@@ -62,6 +69,7 @@ int main(int argc, char **argv) {
   ocffm_param_default(&prm);
   std::string te_path, model_path, binary_path;
   ServeOptions so;
+  ocffm_solve_opts sopt = {0, 0.0, 0};
   try {
     if (argc == 1) throw std::invalid_argument(usage());
     int i = 1;
@@ -86,6 +94,11 @@ int main(int argc, char **argv) {
       else if (a == "--fp32") prm.precision = OCFFM_FP32;
       else if (a == "--fp64") prm.precision = OCFFM_FP64;
       else if (a == "--device") prm.device = std::atoi(value(true, "need a device ordinal after --device"));
+      else if (a == "--objective") {
+        sopt.objective_every = 1;
+        if (i + 1 < argc && is_numerical(argv[i + 1])) sopt.objective_every = (uint32_t)std::atoi(argv[++i]);
+        if (sopt.objective_every == 0) throw std::invalid_argument("--objective takes a period of at least 1");
+      } else if (a == "--tol") sopt.tol = std::atof(value(true, "need to specify the tolerance after --tol"));
       else if (a == "--binary-out") binary_path = value(false, "need to specify path after --binary-out");
       else if (so.take(a, value)) continue;
       else break;
@@ -133,7 +146,8 @@ int main(int argc, char **argv) {
     check(ocffm_problem_init(prob));
     check(ocffm_problem_sync(prob));
     phase("init");
-    check(ocffm_problem_solve(prob));
+    if (sopt.objective_every || sopt.tol > 0) check(ocffm_problem_solve_ex(prob, &sopt, nullptr));
+    else check(ocffm_problem_solve(prob));
     phase("solve");
     if (!model_path.empty()) check(ocffm_problem_save_model(prob, model_path.c_str()));
     if (!binary_path.empty()) check(ocffm_problem_save_binary(prob, binary_path.c_str()));

@@ -68,6 +68,20 @@ class _Eval(C.Structure):
         return d
 
 
+class _Objective(C.Structure):
+    _fields_ = [("value", C.c_double), ("pos", C.c_double), ("on_pos", C.c_double), ("all", C.c_double),
+                ("reg", C.c_double), ("m", C.c_uint64), ("n", C.c_uint64), ("labels", C.c_uint64)]
+
+
+class _SolveOpts(C.Structure):
+    _fields_ = [("objective_every", C.c_uint32), ("tol", C.c_double), ("min_pass", C.c_uint32)]
+
+
+class _SolveReport(C.Structure):
+    _fields_ = [("epochs", C.c_uint32), ("converged", C.c_int32), ("objective0", C.c_double),
+                ("objective", C.c_double)]
+
+
 class _KStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("alg_bytes", C.c_double), ("alg_flops", C.c_double)]
@@ -89,6 +103,7 @@ EXPORTS = [
     "ocffm_data_get_labels", "ocffm_data_get_field", "ocffm_data_free", "ocffm_problem_create", "ocffm_comm_id", "ocffm_problem_create_dist",
     "ocffm_problem_create_dist_host", "ocffm_problem_init", "ocffm_problem_one_epoch",
     "ocffm_problem_solve_block", "ocffm_problem_cache_sasb", "ocffm_problem_solve",
+    "ocffm_problem_objective", "ocffm_problem_solve_ex",
     "ocffm_problem_validate", "ocffm_print_header", "ocffm_print_epoch", "ocffm_problem_get",
     "ocffm_problem_set", "ocffm_problem_grad", "ocffm_problem_hv", "ocffm_problem_save_model",
     "ocffm_problem_validate_forced", "ocffm_problem_test_rows", "ocffm_problem_save_binary", "ocffm_problem_load_binary",
@@ -144,6 +159,8 @@ def lib():
         getattr(L, name).argtypes = [vp]
     L.ocffm_problem_solve_block.argtypes = [vp, u32, u32]
     L.ocffm_problem_validate.argtypes = [vp, C.POINTER(_Metrics)]
+    L.ocffm_problem_objective.argtypes = [vp, C.POINTER(_Objective)]
+    L.ocffm_problem_solve_ex.argtypes = [vp, C.POINTER(_SolveOpts), C.POINTER(_SolveReport)]
     L.ocffm_print_epoch.argtypes = [C.POINTER(_Metrics), u32]
     L.ocffm_problem_get.argtypes = [vp, C.c_char, u32, vp, u64, C.POINTER(u64)]
     L.ocffm_problem_set.argtypes = [vp, C.c_char, u32, vp, u64]
@@ -584,8 +601,28 @@ class ImpProblem:
     def cache_sasb(self):
         _check(lib().ocffm_problem_cache_sasb(self.h))
 
-    def solve(self):
-        _check(lib().ocffm_problem_solve(self.h))
+    def solve(self, objective_every: int = 0, tol: float = 0.0, min_pass: int = 0) -> dict:
+        """``nr_pass`` epochs (ffm.cpp:1147-1161).  ``objective_every=e`` evaluates the
+        objective before the first epoch and after every e-th and prints it; ``tol``
+        stops after the epoch whose relative decrease is at most ``tol`` (not
+        before ``min_pass`` epochs).  Returns ``epochs``, ``converged``,
+        ``objective0`` and ``objective`` (the last two None when never evaluated)."""
+        if objective_every == 0 and tol <= 0.0:
+            _check(lib().ocffm_problem_solve(self.h))
+            return dict(epochs=int(self.param.nr_pass), converged=False, objective0=None, objective=None)
+        o = _SolveOpts(int(objective_every), float(tol), int(min_pass))
+        r = _SolveReport()
+        _check(lib().ocffm_problem_solve_ex(self.h, C.byref(o), C.byref(r)))
+        return dict(epochs=int(r.epochs), converged=bool(r.converged), objective0=r.objective0,
+                    objective=r.objective)
+
+    def objective(self) -> dict:
+        """The training objective of the current state (``ocffm_problem_objective``):
+        ``value = 0.5 (pos + omega (all - on_pos) + reg)`` and its terms."""
+        o = _Objective()
+        _check(lib().ocffm_problem_objective(self.h, C.byref(o)))
+        return dict(value=o.value, pos=o.pos, on_pos=o.on_pos, all=o.all, reg=o.reg, m=int(o.m), n=int(o.n),
+                    labels=int(o.labels))
 
     def validate(self) -> dict:
         m = _Metrics()
