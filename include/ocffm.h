@@ -802,6 +802,10 @@ int ocffm_model_evaluate_among(ocffm_model *m, const ocffm_data *X, const ocffm_
                                const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out);
 int ocffm_model_counter(ocffm_model *m, const char *name, int64_t *value);
 
+/* Folding new users in from an interaction history, on a model: the fold
+ * entries (fold_in and the _fold forms of recommend, label_ranks and evaluate)
+ * are declared in ocffm_fold.h, included at the end of this header. */
+
 /* Access.  ocffm_model_get_info fills Ds / used when the caller gave room;
  * ocffm_model_get_ds writes the f field sizes (user fields first).
  * ocffm_model_get copies to the host as fp64 like ocffm_problem_get: what 'W',
@@ -815,4 +819,7 @@ void ocffm_model_destroy(ocffm_model *m);
 #ifdef __cplusplus
 }
 #endif
+
+#include "ocffm_fold.h"
+
 #endif /* OCFFM_H */

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <limits>
 #include <map>
@@ -19,6 +20,7 @@
 
 #include "../../include/ocffm.h"
 #include "common.hpp"
+#include "fold_kernels.hpp"
 #include "kernels.hpp"
 #include "model_file.h"
 #include "model_source.hpp"
@@ -117,14 +119,25 @@ static void model_check_cuts(const uint32_t *cuts, uint32_t ncut) {
 }
 
 // ------------------------------------------------------------------ model
+// A fold request of a serving call (ocffm_model_fold_in): the history rows and
+// the parameters; delta / nhist (fold_in alone) take the corrections and |H_i|
+// of the call's rows.
+struct FoldSpec {
+  const HostData *hist = nullptr;
+  ocffm_fold fo{};
+  double *delta = nullptr;
+  uint32_t *nhist = nullptr;
+};
+
 struct ModelBase {
   virtual ~ModelBase() = default;
   virtual void set_items(const HostData &V) = 0;
   virtual void set_popularity(const double *pop, uint64_t npop) = 0;
   virtual void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags,
-                         uint32_t *items, double *scores) = 0;
+                         uint32_t *items, double *scores, const FoldSpec *fold) = 0;
   virtual void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
-                           uint32_t *ncand) = 0;
+                           uint32_t *ncand, const FoldSpec *fold) = 0;
+  virtual void fold_in(const HostData &X, const FoldSpec &fold) = 0;
   virtual void score(const HostData &X, uint64_t npairs, const uint32_t *prow, const uint32_t *pitem, double *out) = 0;
   virtual void recommend_among(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr,
                                const uint32_t *ccol, uint32_t topn, uint32_t flags, uint32_t *items,
@@ -228,6 +241,7 @@ template <typename real> class Model final : public ModelBase {
     has_items_ = true;
     popular_.release();
     npop_ = 0;
+    fold_ready_ = false;  // (the aggregates are the old catalogue's)
   }
   void set_popularity(const double *pop, uint64_t npop) override {
     use_device();
@@ -240,17 +254,18 @@ template <typename real> class Model final : public ModelBase {
 
   // ------------------------------------------------------------ serving
   void recommend(const HostData &X, uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
-                 double *scores) override {
+                 double *scores, const FoldSpec *fold) override {
     use_device();
     need_items();
     check_topn(X, row0, rows, topn, items);
+    if (fold) fold_check(X, *fold);
     check_rows(X, row0, rows);
     if (rows == 0) return;
     if (n_ == 0) return none_lists(rows, topn, items, scores);
     begin();
     const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
     Query L;
-    query(L, X, row0, rows, excl ? &X : nullptr);
+    query(L, X, row0, rows, excl ? &X : nullptr, fold);
     const RankModel<real> m = rank_model();
     Rank{*this, m}.recommend(L, rows, topn, excl, items, scores, "rec_setup_us");
     end();
@@ -292,16 +307,17 @@ template <typename real> class Model final : public ModelBase {
     end();
   }
   void label_ranks(const HostData &X, const HostData *seen, uint32_t *ranks, double *scores,
-                   uint32_t *ncand) override {
+                   uint32_t *ncand, const FoldSpec *fold) override {
     use_device();
     need_items();
     label_check(X, seen, ranks);
+    if (fold) fold_check(X, *fold);
     check_rows(X, 0, X.m);
     if (X.m == 0) return;
     if (n_ == 0) return none_ranks(X, ranks, scores, ncand);
     begin();
     Query L;
-    query(L, X, 0, X.m, seen);
+    query(L, X, 0, X.m, seen, fold);
     const RankModel<real> m = rank_model();
     Rank{*this, m}.label_ranks(L, X, seen != nullptr, ranks, scores, ncand, "eval_setup_us");
     end();
@@ -320,6 +336,24 @@ template <typename real> class Model final : public ModelBase {
     query(L, X, 0, X.m, seen);
     const RankModel<real> m = rank_model();
     Rank{*this, m}.label_ranks_among(L, X, cptr, ccol, ranks, scores, ncand, "eval_setup_us");
+    end();
+  }
+
+  // delta_i and |H_i| of every row of X (ocffm_model_fold_in)
+  void fold_in(const HostData &X, const FoldSpec &fold) override {
+    use_device();
+    need_items();
+    fold_check(X, fold);
+    check_rows(X, 0, X.m);
+    const uint64_t d = (uint64_t)fv_ * k_;
+    std::fill(fold.delta, fold.delta + X.m * d, 0.0);
+    if (fold.nhist) std::fill(fold.nhist, fold.nhist + X.m, 0u);
+    counters["fold_us"] = 0;
+    counters["fold_rows"] = 0;
+    if (X.m == 0 || n_ == 0) return;
+    begin();
+    Query L;
+    query(L, X, 0, X.m, nullptr, &fold);
     end();
   }
 
@@ -516,15 +550,174 @@ template <typename real> class Model final : public ModelBase {
     DevBuf<real> tab, ax;
     DevBuf<real *> tp;
   };
-  void query(Query &L, const HostData &X, uint64_t row0, uint64_t rows, const HostData *lab) {
+  void query(Query &L, const HostData &X, uint64_t row0, uint64_t rows, const HostData *lab,
+             const FoldSpec *fold = nullptr) {
     layout(L.sr, X, row0, rows, fu_);
     project(0, L.sr, rows, L.tab, L.tp, L.ax);
     L.cold.resize(rows);
     for (uint64_t i = 0; i < rows; i++) L.cold[i] = X.nnx[row0 + i] == 0;
+    FoldRows fr;
+    if (fold) fold_rows(fr, L, *fold, row0, rows);
     L.dcold.upload(L.cold);
     L.exclusions(lab, row0, rows, n_);
     L.P = L.tp.p;
     L.a = L.ax.p;
+    if (fold) fold_apply(fr, L, *fold, row0, rows);
+  }
+
+  // ------------------------------------------------------------- fold-in
+  // The folded rows of a call (those with a history item < n), compacted, and
+  // their histories: sorted, distinct, < n
+  struct FoldRows {
+    std::vector<uint32_t> frow, hcol;
+    std::vector<int64_t> hptr{0};
+  };
+  void fold_check(const HostData &X, const FoldSpec &fold) const {
+    const ocffm_fold &fo = fold.fo;
+    if (fo.field >= fu_) throw Error(OCFFM_E_ARG, "fold: field is not a user field of the model");
+    if (!std::isfinite(fo.omega) || !std::isfinite(fo.lambda) || !std::isfinite(fo.r) || !(fo.lambda > 0) ||
+        !(fo.omega >= 0))
+      throw Error(OCFFM_E_ARG, "fold: lambda must be > 0, omega >= 0, and omega, lambda, r finite");
+    const HostData &h = *fold.hist;
+    if (h.m != X.m) throw Error(OCFFM_E_ARG, "fold: hist must have X's row count");
+    if (h.m && (!h.has_label || h.yptr.size() != h.m + 1)) throw Error(OCFFM_E_ARG, "fold: hist has no labels");
+    if ((uint64_t)fv_ * k_ > OCFFM_FOLD_MAX_D)
+      throw Error(OCFFM_E_ARG, "fold: fv * k = " + std::to_string((uint64_t)fv_ * k_) +
+                                   " exceeds OCFFM_FOLD_MAX_D = " + std::to_string(OCFFM_FOLD_MAX_D));
+    if (X.m >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many rows");
+  }
+  // Host part, before the cold flags are uploaded: the histories of rows
+  // [row0, row0 + rows); a folded row is not cold
+  void fold_rows(FoldRows &fr, Query &L, const FoldSpec &fold, uint64_t row0, uint64_t rows) {
+    const HostData &h = *fold.hist;
+    for (uint64_t i = 0; i < rows; i++) {
+      const size_t b = fr.hcol.size();
+      for (uint64_t p = h.yptr[row0 + i]; p < h.yptr[row0 + i + 1]; p++)
+        if (h.ycol[p] < n_) fr.hcol.push_back((uint32_t)h.ycol[p]);
+      std::sort(fr.hcol.begin() + b, fr.hcol.end());
+      fr.hcol.erase(std::unique(fr.hcol.begin() + b, fr.hcol.end()), fr.hcol.end());
+      if (fold.nhist) fold.nhist[row0 + i] = (uint32_t)(fr.hcol.size() - b);
+      if (fr.hcol.size() == b) continue;
+      fr.frow.push_back((uint32_t)i);
+      fr.hptr.push_back((int64_t)fr.hcol.size());
+      L.cold[i] = 0;
+    }
+  }
+  // The catalogue aggregates G, s, t in fp64 by the objective's kernels on qt_
+  // / b_, once per catalogue.  The row ranges are a function of n alone and
+  // their partials are summed in range order.
+  void fold_stats() {
+    if (fold_ready_) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t C = C_, ntp = C * (C + 1) / 2;
+    const uint64_t D = (uint64_t)C * kp_, gsz = std::max<uint64_t>(1, (uint64_t)ntp * kp_ * kp_), nvec = 2 * D + 2;
+    const uint32_t G = std::min(2u, std::max(C, 1u)), ng = (C + G - 1) / G, ngp = ng * (ng + 1) / 2;
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1, (256ull << 20) / (gsz * 8)),
+                                            std::max<uint64_t>(1, 1024 / std::max(ngp, 1u)));
+    const uint64_t nbx = std::clamp<uint64_t>((n_ + 31) / 32, 1, cap), rpb = std::max<uint64_t>(1, (n_ + nbx - 1) / nbx);
+    DevBuf<double> part;
+    part.alloc(nbx * std::max(gsz, nvec), false);
+    foldG_.alloc(gsz);
+    foldvec_.alloc(nvec);
+    const real *const *tabs = (const real *const *)qt_.p;
+    with_kp(kp_, [&](auto K) {
+      constexpr int KP = decltype(K)::value;
+      if (C > 0) {
+        const dim3 grid((unsigned)nbx, ngp);
+        const unsigned threads = 64u * std::min<uint32_t>(BLOCK / 64, G * G);
+        bool done = false;
+        if constexpr (obj_mfma_kp<real, KP>()) {
+          if (n_ * kp_ * sizeof(real) < 0xffffff00ull) {  // (the MFMA tiles' buffer views)
+            launch(k_obj_gram<real, KP, true>, grid, threads, 0, (uint64_t)n_, C, tabs, part.p, rpb, G, ng);
+            done = true;
+          }
+        }
+        if (!done) launch(k_obj_gram<real, KP, false>, grid, threads, 0, (uint64_t)n_, C, tabs, part.p, rpb, G, ng);
+        launch(k_reduce_parts<double, double>, (unsigned)((gsz + 15) / 16), BLOCK, 0, nbx, gsz, (uint64_t)0, gsz,
+               (const double *)part.p, (uint64_t)0, (double *)nullptr, foldG_.p);
+      }
+      launch(k_obj_vecs<real, KP>, (unsigned)nbx, BLOCK, 0, (uint64_t)n_, (int)C, tabs, (const real *)b_.p, 0.0, part.p,
+             rpb);
+      launch(k_reduce_parts<double, double>, (unsigned)((nvec + 15) / 16), BLOCK, 0, nbx, nvec, (uint64_t)0, nvec,
+             (const double *)part.p, (uint64_t)0, (double *)nullptr, foldvec_.p);
+    });
+    sync();
+    fold_ready_ = true;
+    counters["fold_stats_builds"]++;
+    counters["fold_stats_us"] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  }
+  // Device part, on the call's projected tables: build, solve, apply
+  void fold_apply(const FoldRows &fr, Query &L, const FoldSpec &fold, uint64_t row0, uint64_t rows) {
+    const uint32_t d = fv_ * k_;
+    const uint64_t nf = fr.frow.size();
+    counters["fold_rows"] = (int64_t)nf;
+    counters["fold_us"] = 0;
+    if (nf == 0) return;
+    fold_stats();
+    DevBuf<uint32_t> dfrow, dhcol;
+    DevBuf<int64_t> dhptr;
+    DevBuf<double> ddelta;
+    DevBuf<int> dbad;
+    dfrow.upload(fr.frow);
+    dhcol.upload(fr.hcol);
+    dhptr.upload(fr.hptr);
+    ddelta.alloc(rows * d);
+    dbad.alloc(1);
+    FoldArgs<real> a{};
+    a.C = C_;
+    a.fv = fv_;
+    a.k = k_;
+    a.field = fold.fo.field;
+    a.d = d;
+    a.omega = fold.fo.omega;
+    a.lambda = fold.fo.lambda;
+    a.r = fold.fo.r;
+    a.P = L.tp.p;
+    a.a = L.ax.p;
+    a.Q = (const real *const *)qt_.p;
+    a.b = b_.p;
+    a.G = foldG_.p;
+    a.vec = foldvec_.p;
+    a.frow = dfrow.p;
+    a.hptr = dhptr.p;
+    a.hcol = dhcol.p;
+    a.delta = ddelta.p;
+    a.bad = dbad.p;
+    // LDS from d: small d keeps several workgroups per CU; above 64 KiB the kernel opts in
+    const size_t smem = fold_lds_bytes(d);
+    if (smem > (160u << 10)) throw Error(OCFFM_E_ARG, "fold: the LDS request exceeds 160 KiB");
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    try {
+      HIPCHK(hipEventRecord(e0, stream_));
+      with_kp(kp_, [&](auto K) {
+        constexpr int KP = decltype(K)::value;
+        if (smem > (64u << 10))
+          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fold_solve<real, KP>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        launch(k_fold_solve<real, KP>, (unsigned)nf, BLOCK, smem, a);
+      });
+      launch(k_fold_apply<real>, (unsigned)((nf * d + BLOCK - 1) / BLOCK), BLOCK, 0, nf, d, k_, kp_, fold.fo.field * fv_,
+             (const uint32_t *)dfrow.p, (const double *)ddelta.p, (real *const *)L.tp.p, L.dcold.p);
+      HIPCHK(hipEventRecord(e1, stream_));
+      sync();
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+      counters["fold_us"] = (int64_t)(1e3 * ms);
+    } catch (...) {
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      throw;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    int bad = 0;
+    HIPCHK(hipMemcpy(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) throw Error(OCFFM_E_DATA, "fold: a pivot of the normal equations was not positive and finite");
+    if (fold.delta)
+      HIPCHK(hipMemcpy(fold.delta + row0 * d, ddelta.p, rows * d * sizeof(double), hipMemcpyDeviceToHost));
   }
   void alloc_items(uint64_t n) {
     qtab_.alloc(std::max<size_t>(1, (size_t)C_ * n * kp_), false);
@@ -652,6 +845,9 @@ template <typename real> class Model final : public ModelBase {
   DevBuf<real> qtab_, b_;
   DevBuf<real *> qt_;
   DevBuf<double> popular_;
+  // the catalogue's fold aggregates (fold_stats): G's tiles; s, t
+  bool fold_ready_ = false;
+  DevBuf<double> foldG_, foldvec_;
   std::chrono::steady_clock::time_point rank_t0_;
   double kernel_us_ = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_;
@@ -745,7 +941,8 @@ int ocffm_model_set_popularity(ocffm_model *mod, const double *pop, uint64_t npo
 }
 int ocffm_model_recommend(ocffm_model *mod, const ocffm_data *X, uint64_t row0, uint64_t rows, uint32_t topn,
                           uint32_t flags, uint32_t *items, double *scores) {
-  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); mod->m->recommend(X->d, row0, rows, topn, flags, items, scores));
+  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
+             mod->m->recommend(X->d, row0, rows, topn, flags, items, scores, nullptr));
 }
 int ocffm_model_score(ocffm_model *mod, const ocffm_data *X, uint64_t npairs, const uint32_t *prow,
                       const uint32_t *pitem, double *out) {
@@ -760,15 +957,26 @@ int ocffm_model_recommend_among(ocffm_model *mod, const ocffm_data *X, uint64_t 
 int ocffm_model_label_ranks(ocffm_model *mod, const ocffm_data *X, const ocffm_data *seen, uint32_t *ranks,
                             double *scores, uint32_t *ncand) {
   MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
-             mod->m->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand));
+             mod->m->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand, nullptr));
 }
 int ocffm_model_label_ranks_among(ocffm_model *mod, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
                                   const uint32_t *ccol, uint32_t *ranks, double *scores, uint32_t *ncand) {
   MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
              mod->m->label_ranks_among(X->d, seen ? &seen->d : nullptr, cptr, ccol, ranks, scores, ncand));
 }
-int ocffm_model_evaluate(ocffm_model *mod, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
-                         uint32_t ncut, ocffm_eval *out) {
+// The fold arguments of an ABI call
+static FoldSpec fold_spec(const ocffm_data *hist, const ocffm_fold *fo, double *delta = nullptr,
+                          uint32_t *nhist = nullptr) {
+  if (!hist || !fo) throw Error(OCFFM_E_ARG, "null hist or fold parameters");
+  FoldSpec fs;
+  fs.hist = &hist->d;
+  fs.fo = *fo;
+  fs.delta = delta;
+  fs.nhist = nhist;
+  return fs;
+}
+static int model_evaluate(ocffm_model *mod, const ocffm_data *X, const ocffm_data *hist, const ocffm_fold *fo,
+                          bool fold, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
   const ocffm_data *Xd = X;
   std::vector<uint32_t> ranks, ncand;
   std::vector<double> scores;
@@ -781,10 +989,35 @@ int ocffm_model_evaluate(ocffm_model *mod, const ocffm_data *X, const ocffm_data
     ranks.resize(d.ycol.size() + 1);
     ncand.resize(d.m + 1);
     scores.resize(d.ycol.size() + 1);
-    mod->m->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data());
+    const FoldSpec fs = fold ? fold_spec(hist, fo) : FoldSpec{};
+    mod->m->label_ranks(d, seen ? &seen->d : nullptr, ranks.data(), scores.data(), ncand.data(), fold ? &fs : nullptr);
   });
   if (st != OCFFM_OK) return st;
   return ocffm_eval_from_ranks(Xd->d.m, Xd->d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+}
+int ocffm_model_evaluate(ocffm_model *mod, const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts,
+                         uint32_t ncut, ocffm_eval *out) {
+  return model_evaluate(mod, X, nullptr, nullptr, false, seen, cuts, ncut, out);
+}
+int ocffm_model_fold_in(ocffm_model *mod, const ocffm_data *X, const ocffm_data *hist, const ocffm_fold *fo,
+                        double *delta, uint32_t *nhist) {
+  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); if (!delta) throw Error(OCFFM_E_ARG, "null delta");
+             const FoldSpec fs = fold_spec(hist, fo, delta, nhist); mod->m->fold_in(X->d, fs));
+}
+int ocffm_model_recommend_fold(ocffm_model *mod, const ocffm_data *X, const ocffm_data *hist, const ocffm_fold *fo,
+                               uint64_t row0, uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items,
+                               double *scores) {
+  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); const FoldSpec fs = fold_spec(hist, fo);
+             mod->m->recommend(X->d, row0, rows, topn, flags, items, scores, &fs));
+}
+int ocffm_model_label_ranks_fold(ocffm_model *mod, const ocffm_data *X, const ocffm_data *hist, const ocffm_fold *fo,
+                                 const ocffm_data *seen, uint32_t *ranks, double *scores, uint32_t *ncand) {
+  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X"); const FoldSpec fs = fold_spec(hist, fo);
+             mod->m->label_ranks(X->d, seen ? &seen->d : nullptr, ranks, scores, ncand, &fs));
+}
+int ocffm_model_evaluate_fold(ocffm_model *mod, const ocffm_data *X, const ocffm_data *hist, const ocffm_fold *fo,
+                              const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
+  return model_evaluate(mod, X, hist, fo, true, seen, cuts, ncut, out);
 }
 int ocffm_model_evaluate_among(ocffm_model *mod, const ocffm_data *X, const ocffm_data *seen, const uint64_t *cptr,
                                const uint32_t *ccol, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {

@@ -10,7 +10,12 @@
 //   into item_file, so this is for the training catalogue;
 //   the serving options of train (serve_cli.hpp), with the same meaning and
 //   the same output bytes: --recommend / --topn / --rec-out / --rec-unseen /
-//   --rec-candidates, --eval / --eval-cuts / --eval-seen / --eval-candidates.
+//   --rec-candidates, --eval / --eval-cuts / --eval-seen / --eval-candidates;
+//   --fold-field <f> --fold-history <labelled file> [--fold-omega w]
+//   [--fold-lambda l] [--fold-r r]: fold every row of the --recommend and
+//   --eval files in from the labels of the same row of the history file
+//   (ocffm_fold.h ocffm_model_fold_in) before it is served; w, l, r default to
+//   train's -w, -l, -r defaults.  Not with the candidate-list options.
 // item_file is the catalogue: any item rows in the model's item field space
 // (read with the model's item Ds, as a test file is with the train Ds).
 #include <chrono>
@@ -31,14 +36,22 @@ static std::string usage() {
          "--fp32 | --fp64: device arithmetic (default fp64)\n"
          "--device <n>: HIP device ordinal\n"
          "--binary: model_file is a binary snapshot (train --binary-out); default: the text model (train -o)\n"
-         "--popularity <path>: labelled train file whose label counts score the rows without features\n" +
+         "--popularity <path>: labelled train file whose label counts score the rows without features\n"
+         "--fold-field <f>: fold the rows in as new values of user field f, from their histories\n"
+         "--fold-history <path>: labelled file, one row per row of the --recommend / --eval file: the items the\n"
+         "                       row's user has touched (only the labels are read)\n"
+         "--fold-omega <w> | --fold-lambda <l> | --fold-r <r>: the fold's parameters (default: train's defaults)\n" +
          serve_usage("");
 }
 
 int main(int argc, char **argv) {
   int precision = OCFFM_FP64, device = 0;
   bool binary = false;
-  std::string pop_path;
+  std::string pop_path, fold_hist;
+  long fold_field = -1;
+  ocffm_param pd;
+  ocffm_param_default(&pd);
+  ocffm_fold fo{0, pd.omega, pd.lambda, pd.r};
   ServeOptions so;
   try {
     if (argc == 1) throw std::invalid_argument(usage());
@@ -56,10 +69,23 @@ int main(int argc, char **argv) {
       else if (a == "--device") device = std::atoi(value(true, "need a device ordinal after --device"));
       else if (a == "--binary") binary = true;
       else if (a == "--popularity") pop_path = value(false, "need to specify path after --popularity");
+      else if (a == "--fold-field") fold_field = std::atol(value(true, "need a user field after --fold-field"));
+      else if (a == "--fold-history") fold_hist = value(false, "need to specify path after --fold-history");
+      else if (a == "--fold-omega") fo.omega = std::atof(value(true, "need a number after --fold-omega"));
+      else if (a == "--fold-lambda") fo.lambda = std::atof(value(true, "need a number after --fold-lambda"));
+      else if (a == "--fold-r") fo.r = std::atof(value(true, "need a number after --fold-r"));
       else if (so.take(a, value)) continue;
       else break;
     }
     so.validate();
+    const bool fold = fold_field >= 0 || !fold_hist.empty();
+    if (fold && (fold_field < 0 || fold_hist.empty()))
+      throw std::invalid_argument("--fold-field and --fold-history go together");
+    if (fold && so.rec_path.empty() && so.eval_path.empty())
+      throw std::invalid_argument("--fold-field needs --recommend or --eval");
+    if (fold && (!so.rec_cand.empty() || !so.eval_cand.empty()))
+      throw std::invalid_argument("--fold-field cannot be combined with the candidate-list options");
+    fo.field = fold ? (uint32_t)fold_field : 0u;
     if (i + 1 >= argc) throw std::invalid_argument("model file and item file not specified");
     if (i + 2 < argc) throw std::invalid_argument(std::string("unexpected argument: ") + argv[i + 2]);
     const std::string model_path = argv[i], item_path = argv[i + 1];
@@ -96,6 +122,8 @@ int main(int argc, char **argv) {
     }
     ServeLists lists;
     lists.read(so, ds.data(), mi.fu);
+    ocffm_data *Hs = nullptr;
+    if (fold) check(ocffm_data_read(fold_hist.c_str(), 1, ds.data(), mi.fu, &Hs));
     phase("read");
     ocffm_model *mod = nullptr;
     check(binary ? ocffm_model_load_binary(model_path.c_str(), precision, device, &mod)
@@ -104,7 +132,8 @@ int main(int argc, char **argv) {
     check(ocffm_model_set_items(mod, V));
     if (!pop.empty()) check(ocffm_model_set_popularity(mod, pop.data(), pop.size()));
     phase("items");
-    serve(ModelServer{mod}, so, lists, ds.data(), mi.fu, phase);
+    serve(ModelServer{mod, Hs, fo}, so, lists, ds.data(), mi.fu, phase);
+    if (Hs) ocffm_data_free(Hs);
     ocffm_model_destroy(mod);
     ocffm_data_free(V);
   } catch (std::invalid_argument &e) {

@@ -166,7 +166,10 @@ struct ProblemServer {
 };
 struct ModelServer {
   ocffm_model *h;
+  const ocffm_data *hist = nullptr;  // predict --fold-history: the rows are folded in first
+  ocffm_fold fo{};
   int recommend(const ocffm_data *X, std::uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+    if (hist) return ocffm_model_recommend_fold(h, X, hist, &fo, 0, rows, topn, flags, items, scores);
     return ocffm_model_recommend(h, X, 0, rows, topn, flags, items, scores);
   }
   int recommend_among(const ocffm_data *X, std::uint64_t rows, const std::uint64_t *cptr, const uint32_t *ccol,
@@ -174,6 +177,7 @@ struct ModelServer {
     return ocffm_model_recommend_among(h, X, 0, rows, cptr, ccol, topn, flags, items, scores);
   }
   int evaluate(const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {
+    if (hist) return ocffm_model_evaluate_fold(h, X, hist, &fo, seen, cuts, ncut, out);
     return ocffm_model_evaluate(h, X, seen, cuts, ncut, out);
   }
   int evaluate_among(const ocffm_data *X, const ocffm_data *seen, const std::uint64_t *cptr, const uint32_t *ccol,

@@ -95,6 +95,10 @@ class _ModelInfo(C.Structure):
                 ("ds_cap", C.c_uint32), ("used_cap", C.c_uint32)]
 
 
+class _Fold(C.Structure):
+    _fields_ = [("field", C.c_uint32), ("omega", C.c_double), ("lambda_", C.c_double), ("r", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p)
 
 EXPORTS = [
@@ -124,6 +128,10 @@ EXPORTS = [
     "ocffm_model_recommend_among", "ocffm_model_label_ranks", "ocffm_model_label_ranks_among",
     "ocffm_model_evaluate", "ocffm_model_evaluate_among", "ocffm_model_counter", "ocffm_model_get_info",
     "ocffm_model_get_ds", "ocffm_model_get", "ocffm_model_destroy",
+]
+# include/ocffm_fold.h (included by ocffm.h): the fold entries of a model
+FOLD_EXPORTS = [
+    "ocffm_model_fold_in", "ocffm_model_recommend_fold", "ocffm_model_label_ranks_fold", "ocffm_model_evaluate_fold",
 ]
 
 _lib = None
@@ -229,6 +237,11 @@ def lib():
     L.ocffm_model_get.argtypes = [vp, C.c_char, u32, vp, u64, C.POINTER(u64)]
     L.ocffm_model_destroy.argtypes = [vp]
     L.ocffm_model_destroy.restype = None
+    fo = C.POINTER(_Fold)
+    L.ocffm_model_fold_in.argtypes = [vp, vp, vp, fo, vp, vp]
+    L.ocffm_model_recommend_fold.argtypes = [vp, vp, vp, fo, u64, u64, u32, u32, vp, vp]
+    L.ocffm_model_label_ranks_fold.argtypes = [vp, vp, vp, fo, vp, vp, vp, vp]
+    L.ocffm_model_evaluate_fold.argtypes = [vp, vp, vp, fo, vp, vp, u32, C.POINTER(_Eval)]
     _lib = L
     return L
 
@@ -884,18 +897,49 @@ class Model:
         _check(lib().ocffm_model_get(self.h, what.encode(), b12, _ptr(out), n.value, C.byref(n)))
         return out
 
+    @staticmethod
+    def _fold(fold, candidates):
+        """``fold=(hist, field, omega, lam, r)`` as the C entries take it."""
+        if candidates is not None:
+            raise ValueError("fold= cannot be combined with candidates=: the list forms do not fold")
+        hist, field, omega, lam, r = fold
+        return hist, _Fold(int(field), float(omega), float(lam), float(r))
+
+    def fold_in(self, X: ImpData, hist: ImpData, field: int, omega: float, lam: float, r: float):
+        """Fold the rows of ``X`` in from their histories, the labels of the
+        same rows of ``hist`` (include/ocffm_fold.h ocffm_model_fold_in):
+        ``(delta, nhist)``, float64 [m, fv * k] (item field major) and uint32
+        [m]; a row without a history item below ``n`` has ``delta == 0``."""
+        i = self.info
+        m, d = int(X.info["m"]), int(i["fv"]) * int(i["k"])
+        delta = np.zeros((m, d), dtype=np.float64)
+        nhist = np.zeros(max(1, m), dtype=np.uint32)
+        fo = _Fold(int(field), float(omega), float(lam), float(r))
+        pad = np.zeros(1, dtype=np.float64)
+        _check(lib().ocffm_model_fold_in(self.h, X.h, None if hist is None else hist.h, C.byref(fo),
+                                         _ptr(delta if delta.size else pad), _ptr(nhist)))
+        return delta, nhist[:m]
+
     def recommend(self, X: ImpData, topn: int = 10, exclude_labels: bool = False, row0: int = 0,
-                  rows: Optional[int] = None, candidates=None):
+                  rows: Optional[int] = None, candidates=None, fold=None):
         """Top-``topn`` catalogue items of rows [row0, row0 + rows) of ``X``
         (include/ocffm.h ocffm_model_recommend): the shape, order and rules of
         ``ImpProblem.recommend``; with ``candidates=(cptr, ccol)`` each row is
-        ranked among its own list (ocffm_model_recommend_among)."""
+        ranked among its own list (ocffm_model_recommend_among); with
+        ``fold=(hist, field, omega, lam, r)`` the rows with a history are
+        folded in first (ocffm_model_recommend_fold)."""
         if rows is None:
             rows = max(0, int(X.info["m"]) - row0)
         shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
         items = np.full(shape, REC_NONE, dtype=np.uint32)
         scores = np.full(shape, -np.inf, dtype=np.float64)
         flags = REC_EXCLUDE_LABELS if exclude_labels else 0
+        if fold is not None:
+            hist, fo = self._fold(fold, candidates)
+            _check(lib().ocffm_model_recommend_fold(self.h, X.h, hist.h, C.byref(fo), row0, rows, topn, flags,
+                                                    items.ctypes.data_as(C.c_void_p),
+                                                    scores.ctypes.data_as(C.c_void_p)))
+            return items, scores
         if candidates is None:
             _check(lib().ocffm_model_recommend(self.h, X.h, row0, rows, topn, flags, items.ctypes.data_as(C.c_void_p),
                                                scores.ctypes.data_as(C.c_void_p)))
@@ -911,20 +955,30 @@ class Model:
         values ``recommend`` returns bit for bit; ``-inf`` for no candidate."""
         return _score(lib().ocffm_model_score, self.h, X, rows, items)
 
-    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None, candidates=None):
+    def label_ranks(self, X: ImpData, seen: Optional[ImpData] = None, candidates=None, fold=None):
         """Exact rank of every label of ``X`` among its row's candidates
         (include/ocffm.h ocffm_model_label_ranks; with ``candidates``
-        ocffm_model_label_ranks_among): ``(ranks, scores, ncand)`` as
+        ocffm_model_label_ranks_among; with ``fold`` as in ``recommend``
+        ocffm_model_label_ranks_fold): ``(ranks, scores, ncand)`` as
         ``ImpProblem.label_ranks``; labels are catalogue indices."""
         L = lib()
+        if fold is not None:
+            hist, fo = self._fold(fold, candidates)
+            return _label_ranks(lambda h, x, sh, *out: L.ocffm_model_label_ranks_fold(h, x, hist.h, C.byref(fo), sh, *out),
+                                None, self.h, X, seen, None)
         return _label_ranks(L.ocffm_model_label_ranks, L.ocffm_model_label_ranks_among, self.h, X, seen, candidates)
 
     def evaluate(self, X: ImpData, cuts=(5, 10, 20, 40, 80), seen: Optional[ImpData] = None,
-                 candidates=None) -> dict:
+                 candidates=None, fold=None) -> dict:
         """Ranking metrics on the labelled rows ``X`` (include/ocffm.h
-        ocffm_model_evaluate; with ``candidates`` ocffm_model_evaluate_among):
-        the dict of ``ImpProblem.evaluate``."""
+        ocffm_model_evaluate; with ``candidates`` ocffm_model_evaluate_among;
+        with ``fold`` as in ``recommend`` ocffm_model_evaluate_fold): the dict
+        of ``ImpProblem.evaluate``."""
         L = lib()
+        if fold is not None:
+            hist, fo = self._fold(fold, candidates)
+            return _evaluate(lambda h, x, sh, *a: L.ocffm_model_evaluate_fold(h, x, hist.h, C.byref(fo), sh, *a),
+                             None, self.h, X, cuts, seen, None)
         return _evaluate(L.ocffm_model_evaluate, L.ocffm_model_evaluate_among, self.h, X, cuts, seen, candidates)
 
     def counter(self, name: str) -> int:
