@@ -18,18 +18,11 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import halves_ref as R
 import oracle_lib as O
 import synth
 
 WORLD = 2
-
-
-def _dense(rows, nfields, dims):
-    X = [np.zeros((rows.m, dims[f])) for f in range(nfields)]
-    for i in range(rows.m):
-        for p in range(int(rows.xptr[i]), int(rows.xptr[i + 1])):
-            X[int(rows.fid[p])][i, int(rows.idx[p])] += rows.val[p]
-    return X
 
 
 def _problem():
@@ -42,76 +35,19 @@ def _problem():
 
 
 def _partials(rank, ds, o, world=WORLD):
-    """This rank's partial gradients / Hv products for every half."""
-    k, w, r, lam = o.k, o.omega, o.r, o.lam
-    fu, f, m, n = o.fu, o.f, o.m, o.n
-    du = [int(x) for x in O.data_ds(O.data_from_rows(ds.train))]
-    dv = [int(x) for x in O.data_ds(O.data_from_rows(ds.item))]
-    Xu, Xv = _dense(ds.train, fu, du), _dense(ds.item, o.fv, dv)
-    Y = np.zeros((m, n))
-    for i in range(m):
-        for p in range(int(ds.train.yptr[i]), int(ds.train.yptr[i + 1])):
-            Y[i, int(ds.train.ycol[p])] = 1.0
-    a, b = o.get("a"), o.get("b")
-    u0, u1 = m * rank // world, m * (rank + 1) // world
-    sh = slice(u0, u1)
-    B = lambda f1, f2: O.block_index(f1, f2, f)  # noqa: E731
-    P = {}
-    Q = {}
-    for f1 in range(f):
-        for f2 in range(f1, f):
-            b12 = B(f1, f2)
-            P[b12] = o.get("P", b12).reshape(-1, k)
-            Q[b12] = o.get("Q", b12).reshape(-1, k)
-    cross = [B(f1, f2) for f1 in range(fu) for f2 in range(fu, f)]
-    yt = a[:, None] + b[None, :] + sum(P[c] @ Q[c].T for c in cross) - 1
-    coef = Y * ((1 - w) * yt - w * (1 - r))
-    sa = sum(P[c] @ Q[c].sum(0) for c in cross)
-    sb_loc = sum(Q[c] @ P[c][sh].sum(0) for c in cross)
+    """This rank's partial gradients / Hv products for every half: the dense
+    restatement (halves_ref.halves) over the rank's user rows, without the
+    lam terms (added once after the all-reduce)."""
+    m = o.m
     rng = np.random.default_rng(7)
-    out = {}
-    for f1 in range(f):
-        for f2 in range(f1, f):
-            b12 = B(f1, f2)
-            for half in (0, 1):
-                fl = f1 if half == 0 else f2
-                user = fl < fu
-                X = Xu[fl] if user else Xv[fl - fu]
-                D = X.shape[1]
-                Q1 = Q[b12] if half == 0 else P[b12]
-                v = rng.standard_normal((D, k))
-                if (f1 < fu) != (f2 < fu):  # cross
-                    if user:
-                        Xs = X[sh]
-                        oQ, bQ = Q1.sum(0), b @ Q1
-                        T = sum(P[c][sh] @ (Q[c].T @ Q1) for c in cross)
-                        g = coef[sh] @ Q1 + w * (T + (a[sh] - r)[:, None] * oQ + bQ)
-                        QTQ = Q1.T @ Q1
-                        phi = Xs @ v
-                        hv = (1 - w) * (((phi @ Q1.T) * Y[sh]) @ Q1) + w * phi @ QTQ
-                    else:
-                        Xs = X
-                        P1 = Q1[sh]
-                        oQ, bQ = P1.sum(0), a[sh] @ P1
-                        T = sum(Q[c] @ (P[c][sh].T @ P1) for c in cross)
-                        g = coef[sh].T @ P1 + w * (T + (b - r)[:, None] * oQ + bQ)
-                        QTQ = P1.T @ P1
-                        phi = Xs @ v
-                        hv = (1 - w) * (((phi @ P1.T) * Y[sh].T) @ P1) + w * phi @ QTQ
-                else:  # side
-                    if user:
-                        Xs, q = X[sh], Q1[sh]
-                        z = w * (n * (a[sh] - r) + b.sum() + sa[sh]) + coef[sh].sum(1)
-                        d = (1 - w) * Y[sh].sum(1) + w * n
-                    else:
-                        Xs, q = X, Q1
-                        z = w * ((u1 - u0) * (b - r) + a[sh].sum() + sb_loc) + coef[sh].sum(0)
-                        d = (1 - w) * Y[sh].sum(0) + w * (u1 - u0)
-                    g = z[:, None] * q
-                    phi = Xs @ v
-                    hv = (d * (phi * q).sum(1))[:, None] * q
-                out[(b12, half)] = (Xs.T @ g, Xs.T @ hv, v)
-    return out
+    vs = {}
+    for f1, f2, b12 in R.used_blocks(o.fu, o.f):
+        for half in (0, 1):
+            D = o.get("W" if half == 0 else "H", b12).size // o.k
+            vs[(b12, half)] = rng.standard_normal((D, o.k))
+    parts = R.halves(ds, R.state_of(o, o.fu, o.f, o.k), dict(k=o.k, omega=o.omega, lam=o.lam, r=o.r), vs=vs,
+                     rows=(m * rank // world, m * (rank + 1) // world), reg=False)
+    return {key: (g, hv, vs[key]) for key, (g, hv) in parts.items()}
 
 
 def _worker(rank, port, result_path, world=WORLD):

@@ -15,6 +15,32 @@ Tolerances (written here):
                reference runs): validation metrics within 3x their spread.
   fp32 mode  : objective and ploss within 1e-3 relative, p@k and nDCG@k
                within 2e-2 absolute (SURVEY §8c measured fp32 drift).
+  per kernel : a half's gradient and Hessian-vector product at init within
+               1e-4 (fp32) / 1e-12 (fp64) of its largest entry.
+  trained state (test_fp32_trained.py, halves_ref.py; both precisions, every
+  padded k but 32):
+               a half at a trained state is held per feature row d to
+               tol x max_c G_abs[d, c] (Hv_abs likewise), tol = 1e-4 / 1e-12,
+               where G_abs is the half's sum with every elementary product
+               replaced by its absolute value: the forward bound
+               n u sum|terms| (n < 1,600 terms on those shapes, u = 2^-24).
+               The scale is the terms', not the result's, because at a trained
+               state the terms cancel (abs-sum 20 to 900 times the largest
+               entry), and per row because a table-wide maximum hides the
+               light rows.  Measured: fp32 <= 0.004, fp64 <= 0.0011 of it.
+               Cached tables (P, Q, a, b, s, t, y~) after an epoch within
+               1e-4 / 1e-11 of the larger of their definition's largest entry
+               before and after the epoch (in-place updates round relative to
+               what they started from).  Measured: fp32 <= 0.005, fp64
+               <= 1.4e-4 of it.
+  one-step regime (the same files): from W, H = float32(2^-7 N(0, 1)) at the
+               smallest lambda of {8, .., 128} at which every half's CG stops
+               after one step on the oracle, a half's update is -alpha G with
+               G the in-epoch gradient, so one epoch compares the in-epoch
+               passes with no CG iteration to amplify fp32 noise: tables
+               within 1e-4 / 1e-9 of their largest reference entry, one CG
+               step per half on both sides.  Measured: fp32 <= 0.015, fp64
+               <= 5.7e-5 of it.  Per case: DESIGN.md §4.
 Init is bit-exact in both modes' source tables: W/H come from the same host
 rand() stream as the reference (ffm.cpp:71-78).
 """
