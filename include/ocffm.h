@@ -806,6 +806,10 @@ int ocffm_model_counter(ocffm_model *m, const char *name, int64_t *value);
  * entries (fold_in and the _fold forms of recommend, label_ranks and evaluate)
  * are declared in ocffm_fold.h, included at the end of this header. */
 
+/* Items like this one: cosine / inner-product top-N between catalogue items,
+ * pair similarities, and queries by item rows that are not in the catalogue
+ * are declared in ocffm_similar.h, included at the end of this header. */
+
 /* Access.  ocffm_model_get_info fills Ds / used when the caller gave room;
  * ocffm_model_get_ds writes the f field sizes (user fields first).
  * ocffm_model_get copies to the host as fp64 like ocffm_problem_get: what 'W',
@@ -821,5 +825,6 @@ void ocffm_model_destroy(ocffm_model *m);
 #endif
 
 #include "ocffm_fold.h"
+#include "ocffm_similar.h"
 
 #endif /* OCFFM_H */

@@ -1,6 +1,7 @@
 // model.hip — the stand-alone model handle (ocffm.h ocffm_model): W / H of a
 // saved or trained model, an item catalogue in the serving sweeps' form, and
-// the serving entries on it.  A third host of the serving driver
+// the serving entries on it, the item-item similarities among them
+// (ocffm_similar.h, sim_kernels.hpp).  A third host of the serving driver
 // (rank_driver.hpp) beside the Newton-CG problem (solver.hip) and the SGD
 // trainer (sgd.hip): the files are read on the host (model_file.cpp), any rows
 // are projected through W / H by one launch (k_project_side), and the sweeps,
@@ -25,6 +26,7 @@
 #include "model_file.h"
 #include "model_source.hpp"
 #include "rank_driver.hpp"
+#include "sim_kernels.hpp"
 
 namespace ocffm {
 
@@ -144,6 +146,12 @@ struct ModelBase {
                                double *scores) = 0;
   virtual void label_ranks_among(const HostData &X, const HostData *seen, const uint64_t *cptr, const uint32_t *ccol,
                                  uint32_t *ranks, double *scores, uint32_t *ncand) = 0;
+  virtual void similar_items(uint64_t nq, const uint32_t *qitem, const uint64_t *xptr, const uint32_t *xcol,
+                             uint32_t topn, uint32_t flags, uint32_t *items, double *scores) = 0;
+  virtual void similar_to(const HostData &Vq, uint64_t row0, uint64_t rows, const uint64_t *xptr, const uint32_t *xcol,
+                          uint32_t topn, uint32_t flags, uint32_t *items, double *scores) = 0;
+  virtual void item_similarity(uint64_t npairs, const uint32_t *pa, const uint32_t *pb, uint32_t flags,
+                               double *out) = 0;
   virtual uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) = 0;
   virtual void info(ocffm_model_info *out) const = 0;
   virtual const std::vector<uint64_t> &ds() const = 0;
@@ -242,6 +250,7 @@ template <typename real> class Model final : public ModelBase {
     popular_.release();
     npop_ = 0;
     fold_ready_ = false;  // (the aggregates are the old catalogue's)
+    sim_ready_ = false;   // (so are the inverse norms)
   }
   void set_popularity(const double *pop, uint64_t npop) override {
     use_device();
@@ -354,6 +363,138 @@ template <typename real> class Model final : public ModelBase {
     begin();
     Query L;
     query(L, X, 0, X.m, nullptr, &fold);
+    end();
+  }
+
+  // ------------------------------------------------------ similar items
+  // Top-N catalogue items by similarity to the catalogue items qitem[0..nq)
+  // (ocffm_similar.h): recommend's sweep in REC_SIM mode; a chunk's query rows
+  // are gathered from the catalogue's own tables just before its sweep, so the
+  // scratch is chunk x depth.
+  void similar_items(uint64_t nq, const uint32_t *qitem, const uint64_t *xptr, const uint32_t *xcol, uint32_t topn,
+                     uint32_t flags, uint32_t *items, double *scores) override {
+    use_device();
+    need_items();
+    sim_check(nq, xptr, xcol, topn, flags, items);
+    if (nq && !qitem) throw Error(OCFFM_E_ARG, "null qitem");
+    for (uint64_t e = 0; e < nq; e++)
+      if (qitem[e] >= n_) throw Error(OCFFM_E_ARG, "query item outside the catalogue");
+    if (nq == 0) return;
+    sim_norms();
+    begin();
+    const bool dot = (flags & OCFFM_SIM_DOT) != 0;
+    RankRows<real> L;
+    const bool excl = sim_exclusions(L, nq, (flags & OCFFM_SIM_KEEP_SELF) ? nullptr : qitem, xptr, xcol);
+    DevBuf<uint32_t> dq;
+    dq.upload(qitem, nq);
+    RankModel<real> m = rank_model();
+    m.sv = dot ? nullptr : siminv_.p;
+    SimRank dr{*this, m};
+    const uint64_t chunk = dr.chunk(nq);
+    DevBuf<real> tab, qinv;
+    DevBuf<real *> tp;
+    tab.alloc((size_t)C_ * chunk * kp_, false);
+    qinv.alloc(chunk, false);
+    std::vector<real *> tl(C_);
+    for (uint32_t c = 0; c < C_; c++) tl[c] = tab.p + (size_t)c * chunk * kp_;
+    tp.upload(tl);
+    L.P = tp.p;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> gev;
+    dr.recommend(L, nq, topn, excl, items, scores, "sim_setup_us", "similar",
+                 [&](RecArgs<real> &g, uint64_t c0, uint64_t cr) {
+                   hipEvent_t ea, eb;
+                   HIPCHK(hipEventCreate(&ea));
+                   HIPCHK(hipEventCreate(&eb));
+                   gev.push_back({ea, eb});
+                   HIPCHK(hipEventRecord(ea, stream_));
+                   with_kp(kp_, [&](auto K) {
+                     constexpr int KP = decltype(K)::value;
+                     // a memory-bound copy: at most 2048 blocks, the threads stride over the rest
+                     const uint64_t vecs = cr * C_ * (KP * sizeof(real) / 16);
+                     const unsigned grid = (unsigned)std::clamp<uint64_t>((vecs + BLOCK - 1) / BLOCK, 1, 2048);
+                     launch(k_sim_gather<real, KP>, grid, BLOCK, 0, cr, (int)C_, dq.p + c0, (const real *const *)qt_.p,
+                            (real *const *)tp.p, dot ? nullptr : siminv_.p, qinv.p);
+                   });
+                   HIPCHK(hipEventRecord(eb, stream_));
+                   sim_args(g);
+                   g.p0 = 0;  // (the chunk's own tables and norms)
+                   g.su = dot ? nullptr : qinv.p;
+                 });
+    double gus = 0;  // (recommend has waited for the stream)
+    for (auto &e : gev) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+      gus += 1e3 * ms;
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    counters["sim_gather_us"] = (int64_t)gus;
+    end();
+  }
+  // The same for rows [row0, row0 + rows) of Vq, item rows in the model's item
+  // field space: projected as the catalogue is, their norms by the catalogue's
+  // kernel
+  void similar_to(const HostData &Vq, uint64_t row0, uint64_t rows, const uint64_t *xptr, const uint32_t *xcol,
+                  uint32_t topn, uint32_t flags, uint32_t *items, double *scores) override {
+    use_device();
+    need_items();
+    if (row0 > Vq.m || rows > Vq.m - row0) throw Error(OCFFM_E_ARG, "row range outside Vq");
+    sim_check(rows, xptr, xcol, topn, flags, items);
+    if (Vq.f > fv_) throw Error(OCFFM_E_ARG, "Vq has more fields than the model's item side");
+    check_nodes(Vq, row0, rows, fv_, fu_);
+    if (rows == 0) return;
+    if (n_ == 0) return none_lists(rows, topn, items, scores);
+    sim_norms();
+    begin();
+    const bool dot = (flags & OCFFM_SIM_DOT) != 0;
+    RankRows<real> L;
+    const bool excl = sim_exclusions(L, rows, nullptr, xptr, xcol);
+    SideRows sr;
+    layout(sr, Vq, row0, rows, fv_);
+    DevBuf<real> tab, bias, qinv;
+    DevBuf<real *> tp;
+    project(1, sr, rows, tab, tp, bias);
+    qinv.alloc(rows, false);
+    if (!dot) prof_launch("similar", 0, [&] { inv_norms((const real *const *)tp.p, rows, qinv.p); });
+    RankModel<real> m = rank_model();
+    m.sv = dot ? nullptr : siminv_.p;
+    L.P = tp.p;
+    L.su = dot ? nullptr : qinv.p;
+    SimRank{*this, m}.recommend(L, rows, topn, excl, items, scores, "sim_setup_us", "similar",
+                                [&](RecArgs<real> &g, uint64_t, uint64_t) { sim_args(g); });
+    end();
+  }
+  // sim of the catalogue pairs (pa[e], pb[e]): k_eval_label_scores in REC_SIM
+  // mode on the catalogue's tables from both sides, the sweep's bits
+  void item_similarity(uint64_t npairs, const uint32_t *pa, const uint32_t *pb, uint32_t flags, double *out) override {
+    use_device();
+    need_items();
+    if (flags & ~(OCFFM_SIM_DOT | OCFFM_SIM_KEEP_SELF)) throw Error(OCFFM_E_ARG, "unknown flag bits");
+    if (npairs && (!pa || !pb || !out)) throw Error(OCFFM_E_ARG, "null pair or output array");
+    if (npairs == 0) return;
+    std::vector<uint32_t> krow, kitem;
+    std::vector<uint64_t> where;
+    for (uint64_t e = 0; e < npairs; e++) {
+      out[e] = -std::numeric_limits<double>::infinity();
+      if (pa[e] >= n_ || pb[e] >= n_) continue;
+      krow.push_back(pa[e]);
+      kitem.push_back(pb[e]);
+      where.push_back(e);
+    }
+    if (kitem.empty()) return;
+    sim_norms();
+    begin();
+    const bool dot = (flags & OCFFM_SIM_DOT) != 0;
+    RankModel<real> m = rank_model();
+    m.sv = dot ? nullptr : siminv_.p;
+    RankRows<real> L;
+    L.P = qt_.p;
+    L.su = m.sv;
+    sync();
+    rank_setup_done("sim_setup_us");
+    const std::vector<double> kv = SimRank{*this, m}.score_pairs(L, krow, kitem, "similar");
+    flush_prof();
+    for (size_t t = 0; t < kv.size(); t++) out[where[t]] = kv[t];
     end();
   }
 
@@ -719,6 +860,69 @@ template <typename real> class Model final : public ModelBase {
     if (fold.delta)
       HIPCHK(hipMemcpy(fold.delta + row0 * d, ddelta.p, rows * d * sizeof(double), hipMemcpyDeviceToHost));
   }
+  // --------------------------------------------------------- similarity
+  static void sim_check(uint64_t nq, const uint64_t *xptr, const uint32_t *xcol, uint32_t topn, uint32_t flags,
+                        const uint32_t *items) {
+    if (topn == 0 || topn > OCFFM_REC_MAX_TOPN) throw Error(OCFFM_E_ARG, "topn must be in 1..OCFFM_REC_MAX_TOPN");
+    if (!items) throw Error(OCFFM_E_ARG, "null items");
+    if (flags & ~(OCFFM_SIM_DOT | OCFFM_SIM_KEEP_SELF)) throw Error(OCFFM_E_ARG, "unknown flag bits");
+    if (nq >= 0xffffffffull) throw Error(OCFFM_E_ARG, "too many queries");
+    if (xptr) check_lists(xptr, xcol, nq);
+    else if (xcol) throw Error(OCFFM_E_ARG, "xcol without xptr");
+  }
+  // Each query's exclusion list as the sweep takes it (sorted, distinct, < n):
+  // the caller's list united with the query's own index (self: null keeps it).
+  // Returns whether any list has an entry.
+  bool sim_exclusions(RankRows<real> &L, uint64_t nq, const uint32_t *self, const uint64_t *xptr,
+                      const uint32_t *xcol) const {
+    L.lptr.assign(nq + 1, 0);
+    L.lcol.clear();
+    for (uint64_t i = 0; i < nq; i++) {
+      const size_t b = L.lcol.size();
+      if (self) L.lcol.push_back(self[i]);
+      if (xptr)
+        for (uint64_t p = xptr[i]; p < xptr[i + 1]; p++)
+          if (xcol[p] < n_) L.lcol.push_back(xcol[p]);
+      std::sort(L.lcol.begin() + b, L.lcol.end());
+      L.lcol.erase(std::unique(L.lcol.begin() + b, L.lcol.end()), L.lcol.end());
+      L.lptr[i + 1] = (int64_t)L.lcol.size();
+    }
+    const bool any = !L.lcol.empty();
+    if (!any) L.lcol.push_back(0);
+    L.dlptr.upload(L.lptr);
+    L.dlcol.upload(L.lcol);
+    return any;
+  }
+  // A REC_SIM sweep reads the two inverse norms and nothing else of the side terms
+  static void sim_args(RecArgs<real> &g) {
+    g.a = nullptr;
+    g.b = nullptr;
+    g.cold = nullptr;
+    g.popular = nullptr;
+  }
+  // k_sim_inv_norm over the R rows of the C tables T
+  void inv_norms(const real *const *T, uint64_t R, real *inv) {
+    if (R == 0) return;
+    with_kp(kp_, [&](auto K) {
+      constexpr int KP = decltype(K)::value;
+      // a memory-bound stream: at most 2048 blocks, the subgroups stride over the rest
+      const unsigned grid = (unsigned)std::min<uint64_t>((R * 16 + BLOCK - 1) / BLOCK, 2048);
+      launch(k_sim_inv_norm<real, KP>, grid, BLOCK, 0, R, (int)C_, T, inv);
+    });
+  }
+  // The catalogue's inverse norms, once per catalogue
+  void sim_norms() {
+    if (sim_ready_) return;
+    sync();
+    const auto t0 = std::chrono::steady_clock::now();
+    siminv_.alloc(std::max<uint64_t>(1, n_), false);
+    inv_norms((const real *const *)qt_.p, n_, siminv_.p);
+    sync();
+    sim_ready_ = true;
+    counters["sim_norm_builds"]++;
+    counters["sim_norm_us"] =
+        (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  }
   void alloc_items(uint64_t n) {
     qtab_.alloc(std::max<size_t>(1, (size_t)C_ * n * kp_), false);
     b_.alloc(std::max<uint64_t>(1, n), false);
@@ -763,8 +967,10 @@ template <typename real> class Model final : public ModelBase {
   }
 
   // ------------------------------------- the driver's host (rank_driver.hpp)
-  using Rank = RankDriver<real, false, Model>;
+  using Rank = RankDriver<real, REC_PLAIN, Model>;
+  using SimRank = RankDriver<real, REC_SIM, Model>;
   friend Rank;
+  friend SimRank;
   RankModel<real> rank_model() const {
     RankModel<real> m;
     m.Q = qt_.p;
@@ -848,6 +1054,9 @@ template <typename real> class Model final : public ModelBase {
   // the catalogue's fold aggregates (fold_stats): G's tiles; s, t
   bool fold_ready_ = false;
   DevBuf<double> foldG_, foldvec_;
+  // the catalogue's inverse norms (sim_norms)
+  bool sim_ready_ = false;
+  DevBuf<real> siminv_;
   std::chrono::steady_clock::time_point rank_t0_;
   double kernel_us_ = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_;
@@ -1037,6 +1246,19 @@ int ocffm_model_evaluate_among(ocffm_model *mod, const ocffm_data *X, const ocff
   });
   if (st != OCFFM_OK) return st;
   return ocffm_eval_from_ranks(Xd->d.m, Xd->d.yptr.data(), ranks.data(), scores.data(), ncand.data(), cuts, ncut, out);
+}
+int ocffm_model_similar_items(ocffm_model *mod, uint64_t nq, const uint32_t *qitem, const uint64_t *xptr,
+                              const uint32_t *xcol, uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+  MODEL_CALL(mod->m->similar_items(nq, qitem, xptr, xcol, topn, flags, items, scores));
+}
+int ocffm_model_similar_to(ocffm_model *mod, const ocffm_data *Vq, uint64_t row0, uint64_t rows, const uint64_t *xptr,
+                           const uint32_t *xcol, uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+  MODEL_CALL(if (!Vq) throw Error(OCFFM_E_ARG, "null Vq");
+             mod->m->similar_to(Vq->d, row0, rows, xptr, xcol, topn, flags, items, scores));
+}
+int ocffm_model_item_similarity(ocffm_model *mod, uint64_t npairs, const uint32_t *pa, const uint32_t *pb,
+                                uint32_t flags, double *out) {
+  MODEL_CALL(mod->m->item_similarity(npairs, pa, pb, flags, out));
 }
 int ocffm_model_counter(ocffm_model *mod, const char *name, int64_t *value) {
   MODEL_CALL(if (!name || !value) throw Error(OCFFM_E_ARG, "null argument");

@@ -16,11 +16,17 @@
 //   --eval files in from the labels of the same row of the history file
 //   (ocffm_fold.h ocffm_model_fold_in) before it is served; w, l, r default to
 //   train's -w, -l, -r defaults.  Not with the candidate-list options.
+//   --similar <file | all> --sim-out <path> [--sim-metric cosine|dot]: the
+//   --topn catalogue items most similar to each query item (ocffm_similar.h
+//   ocffm_model_similar_items; the query itself left out), the queries being
+//   the catalogue indices of the file, one per line, or every item for the
+//   word `all`; the output has --rec-out's format, one line per query.
 // item_file is the catalogue: any item rows in the model's item field space
 // (read with the model's item Ds, as a test file is with the train Ds).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <stdexcept>
 #include <string>
@@ -40,14 +46,43 @@ static std::string usage() {
          "--fold-field <f>: fold the rows in as new values of user field f, from their histories\n"
          "--fold-history <path>: labelled file, one row per row of the --recommend / --eval file: the items the\n"
          "                       row's user has touched (only the labels are read)\n"
-         "--fold-omega <w> | --fold-lambda <l> | --fold-r <r>: the fold's parameters (default: train's defaults)\n" +
+         "--fold-omega <w> | --fold-lambda <l> | --fold-r <r>: the fold's parameters (default: train's defaults)\n"
+         "--similar <path | all>: the --topn items most similar to each catalogue item of this file (one index per\n"
+         "                        line), or to every item for the word all\n"
+         "--sim-out <path>: where the similar items go (--rec-out's format, one line per query item)\n"
+         "--sim-metric cosine | dot: the similarity (default cosine)\n" +
          serve_usage("");
+}
+
+// The query items of --similar: one catalogue index per line (blank lines are
+// skipped).  Throws std::invalid_argument (exit 1).
+static std::vector<std::uint32_t> read_queries(const std::string &path) {
+  std::ifstream in(path);
+  if (!in) throw std::invalid_argument("cannot read " + path);
+  std::vector<std::uint32_t> q;
+  std::string line;
+  for (std::uint64_t ln = 1; std::getline(in, line); ln++) {
+    const char *s = line.c_str();
+    while (*s && std::isspace((unsigned char)*s)) s++;
+    if (!*s) continue;
+    std::uint64_t v = 0;
+    const char *b = s;
+    for (; std::isdigit((unsigned char)*s); s++) {
+      v = v * 10 + (std::uint64_t)(*s - '0');
+      if (v > 0xffffffffull) v = 0xffffffffull;  // (outside any catalogue: the call reports it)
+    }
+    while (*s && std::isspace((unsigned char)*s)) s++;
+    if (s == b || *s)
+      throw std::invalid_argument(path + ": line " + std::to_string(ln) + ": a catalogue index must be a non-negative integer");
+    q.push_back((std::uint32_t)v);
+  }
+  return q;
 }
 
 int main(int argc, char **argv) {
   int precision = OCFFM_FP64, device = 0;
   bool binary = false;
-  std::string pop_path, fold_hist;
+  std::string pop_path, fold_hist, sim_path, sim_out, sim_metric = "cosine";
   long fold_field = -1;
   ocffm_param pd;
   ocffm_param_default(&pd);
@@ -74,6 +109,9 @@ int main(int argc, char **argv) {
       else if (a == "--fold-omega") fo.omega = std::atof(value(true, "need a number after --fold-omega"));
       else if (a == "--fold-lambda") fo.lambda = std::atof(value(true, "need a number after --fold-lambda"));
       else if (a == "--fold-r") fo.r = std::atof(value(true, "need a number after --fold-r"));
+      else if (a == "--similar") sim_path = value(false, "need a path or the word all after --similar");
+      else if (a == "--sim-out") sim_out = value(false, "need to specify path after --sim-out");
+      else if (a == "--sim-metric") sim_metric = value(false, "need cosine or dot after --sim-metric");
       else if (so.take(a, value)) continue;
       else break;
     }
@@ -86,6 +124,9 @@ int main(int argc, char **argv) {
     if (fold && (!so.rec_cand.empty() || !so.eval_cand.empty()))
       throw std::invalid_argument("--fold-field cannot be combined with the candidate-list options");
     fo.field = fold ? (uint32_t)fold_field : 0u;
+    if (!sim_path.empty() && sim_out.empty()) throw std::invalid_argument("--similar needs --sim-out <path>");
+    if (sim_path.empty() && !sim_out.empty()) throw std::invalid_argument("--sim-out needs --similar <path | all>");
+    if (sim_metric != "cosine" && sim_metric != "dot") throw std::invalid_argument("--sim-metric takes cosine or dot");
     if (i + 1 >= argc) throw std::invalid_argument("model file and item file not specified");
     if (i + 2 < argc) throw std::invalid_argument(std::string("unexpected argument: ") + argv[i + 2]);
     const std::string model_path = argv[i], item_path = argv[i + 1];
@@ -122,6 +163,8 @@ int main(int argc, char **argv) {
     }
     ServeLists lists;
     lists.read(so, ds.data(), mi.fu);
+    std::vector<std::uint32_t> simq;
+    if (!sim_path.empty() && sim_path != "all") simq = read_queries(sim_path);
     ocffm_data *Hs = nullptr;
     if (fold) check(ocffm_data_read(fold_hist.c_str(), 1, ds.data(), mi.fu, &Hs));
     phase("read");
@@ -133,6 +176,30 @@ int main(int argc, char **argv) {
     if (!pop.empty()) check(ocffm_model_set_popularity(mod, pop.data(), pop.size()));
     phase("items");
     serve(ModelServer{mod, Hs, fo}, so, lists, ds.data(), mi.fu, phase);
+    if (!sim_path.empty()) {
+      if (sim_path == "all") {
+        ocffm_data_info vi;
+        check(ocffm_data_get_info(V, &vi));
+        simq.resize(vi.m);
+        for (std::uint64_t j = 0; j < vi.m; j++) simq[j] = (std::uint32_t)j;
+      }
+      const std::uint64_t nq = simq.size();
+      const long topn = so.topn;
+      std::vector<uint32_t> items(nq * (size_t)topn + 1);
+      std::vector<double> scores(nq * (size_t)topn + 1);
+      simq.push_back(0);  // (a pointer for an empty file)
+      check(ocffm_model_similar_items(mod, nq, simq.data(), nullptr, nullptr, (uint32_t)topn,
+                                      sim_metric == "dot" ? OCFFM_SIM_DOT : 0u, items.data(), scores.data()));
+      std::FILE *fp = std::fopen(sim_out.c_str(), "w");
+      if (!fp) throw Fail(OCFFM_E_IO, "cannot write " + sim_out);
+      for (std::uint64_t i = 0; i < nq; i++) {
+        for (long t = 0; t < topn && items[i * topn + t] != OCFFM_REC_NONE; t++)
+          std::fprintf(fp, t ? " %u:%.17g" : "%u:%.17g", items[i * topn + t], scores[i * topn + t]);
+        std::fputc('\n', fp);
+      }
+      if (std::fclose(fp) != 0) throw Fail(OCFFM_E_IO, "write failed: " + sim_out);
+      phase("similar");
+    }
     if (Hs) ocffm_data_free(Hs);
     ocffm_model_destroy(mod);
     ocffm_data_free(V);

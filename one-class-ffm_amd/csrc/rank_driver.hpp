@@ -14,8 +14,11 @@
 //   resident(kernel, smem)                       blocks of kernel resident on the GPU
 //   sync()                                       wait for the stream
 //   rank_setup_done(counter)                     the call's host set-up ends here
-// NORM: the normalised scores of the SGD model (rank_kernels.hpp rec_score);
-// the Newton problem's instantiations are NORM = false.
+// MODE (rank_kernels.hpp RecMode, rec_score): REC_PLAIN for the Newton
+// problem and the model handle, REC_NORM for the normalised scores of the SGD
+// model, REC_SIM for the model handle's item-item similarities, which use
+// recommend() and score_pairs() alone (the other entries' kernels have no such
+// instantiation).
 #pragma once
 
 #include <algorithm>
@@ -63,7 +66,7 @@ inline void check_lists(const uint64_t *cptr, const uint32_t *ccol, uint64_t row
 template <typename real> struct RankModel {
   const real *const *Q = nullptr;    // C item-side cross tables (n x kp)
   const real *b = nullptr;           // b_j
-  const real *sv = nullptr;          // NORM: the items' squared norms
+  const real *sv = nullptr;          // REC_NORM: the items' squared norms; REC_SIM: their inverse norms (null: 1)
   const double *popular = nullptr;   // cold rows' scores (no cold rows: null)
   uint64_t n = 0, npop = 0;          // items; popularity entries (<= n)
   uint32_t C = 0, kp = 0;
@@ -84,7 +87,7 @@ template <typename real> struct RankModel {
 template <typename real> struct RankRows {
   const real *const *P = nullptr;    // C user-side cross tables of the rows (rows x kp)
   const real *a = nullptr;           // a_i
-  const real *su = nullptr;          // NORM: the rows' squared norms
+  const real *su = nullptr;          // REC_NORM: the rows' squared norms; REC_SIM: their inverse norms (null: 1)
   std::vector<uint8_t> cold;         // (all zero without cold rows)
   DevBuf<uint8_t> dcold;
   std::vector<int64_t> lptr;
@@ -116,7 +119,7 @@ struct RankPlan {
   uint64_t chunk, S, per;  // rows per launch; item slices; items per slice (multiple of REC_IT)
 };
 
-template <typename real, bool NORM, class Host> struct RankDriver {
+template <typename real, RecMode MODE, class Host> struct RankDriver {
   Host &h;
   const RankModel<real> &m;
 
@@ -162,7 +165,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
     g.popular = m.popular;
     g.lptr = L.dlptr.p + c0;
     g.lcol = L.dlcol.p;
-    g.su = NORM ? L.su + c0 : nullptr;
+    g.su = (MODE != REC_PLAIN && L.su) ? L.su + c0 : nullptr;
     g.sv = m.sv;
   }
   // Scores of the pairs (krow[e] of L, kitem[e]), every one a candidate, timed under `family`
@@ -178,7 +181,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
     h.prof_launch(family, (double)nk * (2 * depth * sizeof(real) + sizeof(double) + 2 * sizeof(uint32_t)), [&] {
       with_kp(m.kp, [&](auto K) {
         constexpr int KP = decltype(K)::value;
-        h.launch(k_eval_label_scores<real, KP, NORM>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)m.C,
+        h.launch(k_eval_label_scores<real, KP, MODE>, (unsigned)((nk + 63) / 64), BLOCK, 0, nk, (int)m.C,
                  (const real *const *)L.P, (const real *const *)m.Q, (const real *)L.a, (const real *)m.b,
                  (const uint8_t *)L.dcold.p, (const double *)m.popular, (const uint32_t *)dkrow.p,
                  (const uint32_t *)dkitem.p, dkv.p, (const real *)L.su, (const real *)m.sv);
@@ -201,9 +204,17 @@ template <typename real, bool NORM, class Host> struct RankDriver {
   // ---------------------------------------------------- recommendation
   // Top-N items of the rows of L.  The rows are scored in chunks: scratch is
   // chunk x slices x topn partial entries, never rows x n.
+  // prep(g, c0, cr), inside the chunk's timed launches and before its sweep:
+  // the caller's own launches for rows [c0, c0 + cr) and changes to the
+  // sweep's arguments (similar_items gathers the chunk's query rows there).
   void recommend(const RankRows<real> &L, uint64_t rows, uint32_t topn, bool excl, uint32_t *items, double *scores,
                  const char *setup_counter) {
-    const RankPlan pl = plan(rows, [](auto K) { return k_rec_topn<real, decltype(K)::value, NORM>; });
+    recommend(L, rows, topn, excl, items, scores, setup_counter, "recommend", [](RecArgs<real> &, uint64_t, uint64_t) {});
+  }
+  template <class Prep>
+  void recommend(const RankRows<real> &L, uint64_t rows, uint32_t topn, bool excl, uint32_t *items, double *scores,
+                 const char *setup_counter, const char *family, Prep &&prep) {
+    const RankPlan pl = plan(rows, [](auto K) { return k_rec_topn<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = pl.chunk, S = pl.S;
     DevBuf<double> part_v, out_v;
     DevBuf<uint32_t> part_j, out_j;
@@ -223,10 +234,11 @@ template <typename real, bool NORM, class Host> struct RankDriver {
       const double depth = (double)m.C * m.kp;
       const double bytes = ((double)cr + (double)m.n) * depth * sizeof(real) + (double)m.n * sizeof(real) +
                            (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
-      h.prof_launch("recommend", bytes, [&] {
+      h.prof_launch(family, bytes, [&] {
+        prep(g, c0, cr);
         with_kp(m.kp, [&](auto K) {
           constexpr int KP = decltype(K)::value;
-          h.launch(k_rec_topn<real, KP, NORM>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
+          h.launch(k_rec_topn<real, KP, MODE>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
         });
         h.launch(k_rec_merge, (unsigned)cr, BLOCK, 0, cr, (int)S, (int)topn, (const double *)part_v.p,
                  (const uint32_t *)part_j.p, out_j.p, out_v.p);
@@ -329,7 +341,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
   void rerank(const RankRows<real> &L, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol, uint32_t topn,
               bool excl, uint32_t *items, double *scores, const char *setup_counter) {
     ListPlan p;
-    plan_lists(p, rows, cptr, [](auto K) { return k_rerank<real, decltype(K)::value, NORM>; });
+    plan_lists(p, rows, cptr, [](auto K) { return k_rerank<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = p.chunk;
     DevBuf<uint32_t> part_j, out_j;
     DevBuf<double> part_v, out_v;
@@ -382,7 +394,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
         if (g.W)
           with_kp(m.kp, [&](auto K) {
             constexpr int KP = decltype(K)::value;
-            h.launch(k_rerank<real, KP, NORM>, (unsigned)((g.W + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, g);
+            h.launch(k_rerank<real, KP, MODE>, (unsigned)((g.W + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, g);
           });
         h.launch(k_rerank_merge, (unsigned)((cr + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, cr, c0, g.w0, (int)topn,
                  (const int64_t *)p.dwptr.p, (const double *)part_v.p, (const uint32_t *)part_j.p, out_j.p, out_v.p);
@@ -504,7 +516,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
       h.rank_setup_done(setup_counter);
       return;
     }
-    const RankPlan pl = plan(rows, [](auto K) { return k_eval_count<real, decltype(K)::value, NORM>; });
+    const RankPlan pl = plan(rows, [](auto K) { return k_eval_count<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = pl.chunk;
     h.sync();
     h.rank_setup_done(setup_counter);
@@ -526,7 +538,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
         h.prof_launch("evaluate", bytes, [&] {
           with_kp(m.kp, [&](auto K) {
             constexpr int KP = decltype(K)::value;
-            h.launch(k_eval_count<real, KP, NORM>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
+            h.launch(k_eval_count<real, KP, MODE>, (unsigned)((uint64_t)g.rt * g.S), BLOCK, 0, g);
           });
         }, 2.0 * (double)cr * (double)m.n * depth);
       }
@@ -575,7 +587,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
       return;
     }
     ListPlan p;
-    plan_lists(p, rows, dptr.data(), [](auto K) { return k_rerank_count<real, decltype(K)::value, NORM>; });
+    plan_lists(p, rows, dptr.data(), [](auto K) { return k_rerank_count<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = p.chunk;
     h.sync();
     h.rank_setup_done(setup_counter);
@@ -615,7 +627,7 @@ template <typename real, bool NORM, class Host> struct RankDriver {
         h.prof_launch("evaluate", bytes, [&] {
           with_kp(m.kp, [&](auto K) {
             constexpr int KP = decltype(K)::value;
-            h.launch(k_rerank_count<real, KP, NORM>, (unsigned)((g.W + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, g);
+            h.launch(k_rerank_count<real, KP, MODE>, (unsigned)((g.W + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, g);
           });
         }, 2.0 * (double)nc * depth);
         // (the next chunk's entries overwrite dccol: the copy is ordered after this launch on the stream)

@@ -1,7 +1,8 @@
 // rank_kernels.hpp — the serving kernels: top-N recommendation, ranking
 // evaluation, top-N and label ranks among candidate lists.  Included through rank_driver.hpp
-// by solver.hip (the block Newton-CG problem: NORM = false) and by sgd.hip
-// (the SGD trainer's model: NORM = true), after kernels.hpp.
+// by solver.hip (the block Newton-CG problem: REC_PLAIN), by sgd.hip (the SGD
+// trainer's model: REC_NORM) and by model.hip (REC_PLAIN, and REC_SIM for the
+// item-item similarities: sim_kernels.hpp), after kernels.hpp.
 #pragma once
 
 #include "kernels.hpp"
@@ -37,6 +38,13 @@ constexpr int REC_RT = 32, REC_IT = 64, REC_MAX = 128;
 constexpr uint32_t REC_NONE = 0xffffffffu;
 constexpr double REC_NEG_INF = -__builtin_huge_val();
 
+// How a chain's sum becomes a score (rec_score)
+enum RecMode : int {
+  REC_PLAIN = 0,  // (acc + b_j) + a_i; cold rows rank the popularity
+  REC_NORM = 1,   // the SGD model: the same times 1 / (su_i + sv_j)
+  REC_SIM = 2,    // item-item similarity: acc (inv_i inv_j), the inverse norms in the su / sv slots
+};
+
 // What a sweep over the items needs (rec_sweep); k_rec_topn and k_eval_count
 // add their own.
 template <typename real> struct SweepArgs {
@@ -51,7 +59,8 @@ template <typename real> struct SweepArgs {
   const double *popular;
   const int64_t *lptr;         // sorted, distinct items < n of each query row to leave out (exclude)
   const uint32_t *lcol;
-  const real *su, *sv;         // NORM: squared norms of the query rows, of the items
+  const real *su, *sv;         // REC_NORM: squared norms of the query rows, of the items;
+                               // REC_SIM: their inverse norms (both null: 1, the inner product)
 };
 template <typename real> struct RecArgs : SweepArgs<real> {
   int topn;
@@ -134,21 +143,32 @@ __device__ __forceinline__ bool rec_in_sorted(const uint32_t *col, int64_t lo, i
   return lo < end && col[lo] == j;
 }
 
-// A pair's score from its chain's sum acc: (acc + b_j) + a_i; NORM (the SGD
+// A pair's score from its chain's sum acc: (acc + b_j) + a_i; REC_NORM (the SGD
 // model, sgd.hip): times rn = 1 / (su_i + sv_j), the instance's squared norm
 // (rn = 1 where that is 0: no node, or a model trained without the
-// normalisation, whose su and sv are zero).  The one text of the sweep and of
+// normalisation, whose su and sv are zero).  REC_SIM (ocffm_similar.h): su and
+// sv are the two inverse norms and the score is acc (su sv); their product
+// comes first and commutes, so the score of (x, y) has the bits of (y, x); a_i
+// and b_j play no part.  The one text of the sweep and of
 // k_eval_label_scores, so a pair has the same bits in both.  The division is
 // correctly rounded: its result does not depend on the code around it.
-template <bool NORM, typename real>
+template <RecMode MODE, typename real>
 __device__ __forceinline__ real rec_score(real acc, real bj, real ai, real su, real sv) {
-  const real s = (acc + bj) + ai;
-  if constexpr (NORM) {
-    const real d = su + sv;
-    return s * (d > (real)0 ? (real)1 / d : (real)1);
+  if constexpr (MODE == REC_SIM) {
+    return acc * (su * sv);
   } else {
-    return s;
+    const real s = (acc + bj) + ai;
+    if constexpr (MODE == REC_NORM) {
+      const real d = su + sv;
+      return s * (d > (real)0 ? (real)1 / d : (real)1);
+    } else {
+      return s;
+    }
   }
+}
+// REC_SIM: an inverse norm from its array (null: the inner product, 1)
+template <typename real> __device__ __forceinline__ real rec_inv(const real *inv, uint64_t i) {
+  return inv ? inv[i] : (real)1;
 }
 
 // 4 consecutive depth elements of a row, and the MFMA of one of them
@@ -196,16 +216,17 @@ __device__ __forceinline__ typename RecMma<real>::V rec_ld(const real *const *T,
 // Every tile's scores go through sc; then consume(il, i, j, v, cand) runs once
 // per row of this wave (row il of the tile, i of the launch) with the lane's
 // item j, its score v and whether it is a candidate so far: inside the slice
-// and, for a cold row, below npop (NORM: no row is cold, g.cold and
-// g.popular are not read).  Block-uniform call, after a barrier that
+// and, for a cold row, below npop (REC_NORM and REC_SIM: no row is cold, g.cold
+// and g.popular are not read; REC_SIM reads neither g.a nor g.b).  Block-uniform call, after a barrier that
 // covers the caller's own LDS set-up; what consume writes to LDS for another
 // tile's call of the same row needs no barrier of its own.
-template <typename real, int KP, bool NORM, typename F>
+template <typename real, int KP, RecMode MODE, typename F>
 __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0, uint64_t sl,
                                           double (&sc)[REC_RT][REC_IT + 1], F &&consume) {
   using M = RecMma<real>;
   using V = typename M::V;
   constexpr int GR = M::GR;
+  constexpr bool NORM = MODE == REC_NORM, SIM = MODE == REC_SIM;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int m = lane & 15, q = lane >> 4;
   const uint64_t jb = sl * g.per < g.n ? sl * g.per : g.n;
@@ -220,12 +241,13 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const uint64_t i = r0 + 16 * h + M::drow(q, r);
-      ai[h][r] = i < g.R ? g.a[i] : (real)0;
-      sui[h][r] = (NORM && i < g.R) ? g.su[i] : (real)0;
+      ai[h][r] = (!SIM && i < g.R) ? g.a[i] : (real)0;
+      if constexpr (SIM) sui[h][r] = i < g.R ? rec_inv(g.su, i) : (real)0;
+      else sui[h][r] = (NORM && i < g.R) ? g.su[i] : (real)0;
     }
   // the selection's rows of this wave: REC_RT / 4 of them, cold flags as bits
   unsigned coldbits = 0;
-  if constexpr (!NORM)
+  if constexpr (MODE == REC_PLAIN)
     for (int rr = 0; rr < REC_RT / 4; rr++) {
       const uint64_t i = r0 + w * (REC_RT / 4) + rr;
       if (i < g.R && g.cold[i]) coldbits |= 1u << rr;
@@ -263,8 +285,10 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
   load(std::integral_constant<int, 0>(), 0);
   for (uint64_t t0 = jb; t0 < je; t0 += REC_IT) {
     V acc0 = zero, acc1 = zero;
-    const real bj = hb ? g.b[jq] : (real)0;
-    const real svj = (NORM && hb) ? g.sv[jq] : (real)0;
+    const real bj = (!SIM && hb) ? g.b[jq] : (real)0;
+    real svj = (real)0;
+    if constexpr (SIM) svj = hb ? rec_inv(g.sv, jq) : (real)0;
+    else if constexpr (NORM) svj = hb ? g.sv[jq] : (real)0;
     for (int c0 = 0; c0 < nch; c0 += 2 * GR) {
       load(std::integral_constant<int, 1>(), c0 + GR);
       mma(std::integral_constant<int, 0>(), c0, acc0, acc1);
@@ -279,8 +303,8 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int i0 = M::drow(q, r);
-      sc[i0][w * 16 + m] = (double)rec_score<NORM>(acc0[r], bj, ai[0][r], sui[0][r], svj);
-      sc[16 + i0][w * 16 + m] = (double)rec_score<NORM>(acc1[r], bj, ai[1][r], sui[1][r], svj);
+      sc[i0][w * 16 + m] = (double)rec_score<MODE>(acc0[r], bj, ai[0][r], sui[0][r], svj);
+      sc[16 + i0][w * 16 + m] = (double)rec_score<MODE>(acc1[r], bj, ai[1][r], sui[1][r], svj);
     }
     __syncthreads();
     // wave w takes rows 8 w .. 8 w + 7, lane = the tile's item
@@ -303,7 +327,7 @@ __device__ __forceinline__ void rec_sweep(const SweepArgs<real> &g, uint64_t r0,
   }
 }
 
-template <typename real, int KP, bool NORM = false>
+template <typename real, int KP, RecMode MODE = REC_PLAIN>
 __global__ __launch_bounds__(BLOCK) void k_rec_topn(RecArgs<real> g) {
   __shared__ double sc[REC_RT][REC_IT + 1];
   __shared__ double lv[REC_RT][REC_MAX];
@@ -324,7 +348,7 @@ __global__ __launch_bounds__(BLOCK) void k_rec_topn(RecArgs<real> g) {
   }
   __syncthreads();
   // selection: the threshold first, so the search runs on few candidates
-  rec_sweep<real, KP, NORM>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
+  rec_sweep<real, KP, MODE>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
     double tv = thr_v[il];
     uint32_t tj = thr_j[il];
     cand = cand && rec_better(v, (uint32_t)j, tv, tj);
@@ -409,7 +433,7 @@ static __global__ __launch_bounds__(BLOCK) void k_rec_merge(uint64_t R, int S, i
 // chain (chunks of 16 depth elements in order, then rec_score), so the
 // diagonal of the 16 x 16 product holds each pair's score with the bits the
 // sweep gives it: an output element depends only on its own row and item.
-template <typename real, int KP, bool NORM = false>
+template <typename real, int KP, RecMode MODE = REC_PLAIN>
 __global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, const real *const *__restrict__ P,
                                                              const real *const *__restrict__ Q,
                                                              const real *__restrict__ a, const real *__restrict__ b,
@@ -438,8 +462,11 @@ __global__ __launch_bounds__(BLOCK) void k_eval_label_scores(uint64_t L, int C, 
 #pragma unroll
   for (int r = 0; r < 4; r++)
     if (M::drow(q, r) == m) {
-      if constexpr (NORM) out[e] = (double)rec_score<true>(acc[r], b[item], a[row], su[row], sv[item]);
-      else out[e] = cold[row] ? popular[item] : (double)rec_score<false>(acc[r], b[item], a[row], (real)0, (real)0);
+      if constexpr (MODE == REC_SIM)
+        out[e] = (double)rec_score<REC_SIM>(acc[r], (real)0, (real)0, rec_inv(su, row), rec_inv(sv, item));
+      else if constexpr (MODE == REC_NORM)
+        out[e] = (double)rec_score<REC_NORM>(acc[r], b[item], a[row], su[row], sv[item]);
+      else out[e] = cold[row] ? popular[item] : (double)rec_score<REC_PLAIN>(acc[r], b[item], a[row], (real)0, (real)0);
     }
 }
 
@@ -467,7 +494,7 @@ template <typename real> struct EvalArgs : SweepArgs<real> {  // (lptr / lcol: t
   uint32_t *cnt;               // per label: candidates between the label before it and itself
 };
 
-template <typename real, int KP, bool NORM = false>
+template <typename real, int KP, RecMode MODE = REC_PLAIN>
 __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
   __shared__ double sc[REC_RT][REC_IT + 1];
   __shared__ uint32_t cnt[REC_RT][EV_CAP];
@@ -505,7 +532,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_count(EvalArgs<real> g) {
     if (!any) return;
   }
   // counting: the last label first, so the search runs on few candidates
-  rec_sweep<real, KP, NORM>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
+  rec_sweep<real, KP, MODE>(g, r0, sl, sc, [&](int il, uint64_t i, uint64_t j, double v, bool cand) {
     const int np = kn[il];
     if (np == 0) return;
     cand = cand && rec_better(v, (uint32_t)j, last_v[il], last_j[il]);
@@ -599,7 +626,7 @@ template <typename real> struct RerankArgs {
   const double *popular;
   const int64_t *lptr;         // sorted, distinct labels < n of each row of the call (exclude)
   const uint32_t *lcol;
-  const real *su, *sv;         // NORM: squared norms of the call's rows, of the items
+  const real *su, *sv;         // REC_NORM: squared norms of the call's rows, of the items
   const int64_t *wptr;         // per row of the call: its work items [wptr[i], wptr[i + 1])
   const uint32_t *wrow;        // work item -> row of the call
   const uint64_t *wbeg;        // work item -> its first list entry (an index of the call's ccol)
@@ -609,8 +636,10 @@ template <typename real> struct RerankArgs {
   uint32_t *part_j, *out_j;
 };
 
-template <typename real, int KP, bool NORM = false>
+template <typename real, int KP, RecMode MODE = REC_PLAIN>
 __global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
+  static_assert(MODE != REC_SIM, "the list kernels have no similarity mode");
+  constexpr bool NORM = MODE == REC_NORM;
   using M = RecMma<real>;
   using V = typename M::V;
   const int lane = threadIdx.x & 63;
@@ -659,7 +688,7 @@ __global__ __launch_bounds__(BLOCK) void k_rerank(RerankArgs<real> g) {
 #pragma unroll
         for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
       }
-      if (valid) v = (double)rec_score<NORM>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
+      if (valid) v = (double)rec_score<MODE>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
     }
     const bool cand = valid && q == 0 && rec_better(v, j, tv, tj);
     rec_offer<true>(__ballot(cand), v, j, v0, j0, v1, j1, tv, tj, g.topn, lane);
@@ -744,7 +773,7 @@ template <typename real> struct RerankCountArgs {
   const real *a, *b;           // a_i of the call's rows, b_j
   const uint8_t *cold;         // per row of the call
   const double *popular;
-  const real *su, *sv;         // NORM: squared norms of the call's rows, of the items
+  const real *su, *sv;         // REC_NORM: squared norms of the call's rows, of the items
   const uint32_t *wrow;        // work item -> row of the call
   const uint64_t *wbeg;        // work item -> its first entry (an index of the call's sets)
   const uint32_t *wlen;        // work item -> entries
@@ -755,8 +784,10 @@ template <typename real> struct RerankCountArgs {
   uint32_t *cnt;               // per label: candidates between the label before it and itself
 };
 
-template <typename real, int KP, bool NORM = false>
+template <typename real, int KP, RecMode MODE = REC_PLAIN>
 __global__ __launch_bounds__(BLOCK) void k_rerank_count(RerankCountArgs<real> g) {
+  static_assert(MODE != REC_SIM, "the list kernels have no similarity mode");
+  constexpr bool NORM = MODE == REC_NORM;
   using M = RecMma<real>;
   using V = typename M::V;
   const int lane = threadIdx.x & 63;
@@ -806,7 +837,7 @@ __global__ __launch_bounds__(BLOCK) void k_rerank_count(RerankCountArgs<real> g)
 #pragma unroll
         for (int s = 0; s < 4; s++) acc = M::mma(av[s], bv[s], acc);
       }
-      if (have) v = (double)rec_score<NORM>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
+      if (have) v = (double)rec_score<MODE>(acc[0], g.b[j], ai, sui, NORM ? g.sv[j] : (real)0);
     }
     // counting: the last label first, so the search runs on few entries
     const bool cand = have && q == 0 && rec_better(v, j, last_v, last_j);

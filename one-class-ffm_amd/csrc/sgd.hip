@@ -800,7 +800,7 @@ class Trainer {
   }
   // What the driver needs of its host (rank_driver.hpp); the timing hook sums
   // the launches' time between HIP events on the trainer's stream
-  using Rank = RankDriver<float, true, Trainer>;
+  using Rank = RankDriver<float, REC_NORM, Trainer>;
   friend Rank;
   template <typename... KArgs, typename... A>
   void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t smem, A... a) {

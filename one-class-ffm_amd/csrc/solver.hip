@@ -1215,7 +1215,7 @@ template <typename real> class Problem final : public ProblemBase {
     L.a = L.ax.p;
   }
   // The serving sweeps' driver (rank_driver.hpp) on this problem's item side
-  using Rank = RankDriver<real, false, Problem>;
+  using Rank = RankDriver<real, REC_PLAIN, Problem>;
   friend Rank;
   RankModel<real> rank_model() {
     RankModel<real> m;

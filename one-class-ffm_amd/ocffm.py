@@ -25,6 +25,7 @@ OK, E_ARG, E_IO, E_DATA, E_HIP, E_COMM, E_STATE = range(7)
 FP64, FP32 = 64, 32
 REC_MAX_TOPN, REC_EXCLUDE_LABELS, REC_NONE = 128, 1, 0xFFFFFFFF
 RANK_NONE, EVAL_MAX_CUTS = 0xFFFFFFFF, 8
+SIM_DOT, SIM_KEEP_SELF = 1, 2
 COMM_ID_BYTES = 128
 
 
@@ -133,6 +134,8 @@ EXPORTS = [
 FOLD_EXPORTS = [
     "ocffm_model_fold_in", "ocffm_model_recommend_fold", "ocffm_model_label_ranks_fold", "ocffm_model_evaluate_fold",
 ]
+# include/ocffm_similar.h (included by ocffm.h): items like this one, on a model
+SIMILAR_EXPORTS = ["ocffm_model_similar_items", "ocffm_model_similar_to", "ocffm_model_item_similarity"]
 
 _lib = None
 
@@ -242,6 +245,9 @@ def lib():
     L.ocffm_model_recommend_fold.argtypes = [vp, vp, vp, fo, u64, u64, u32, u32, vp, vp]
     L.ocffm_model_label_ranks_fold.argtypes = [vp, vp, vp, fo, vp, vp, vp, vp]
     L.ocffm_model_evaluate_fold.argtypes = [vp, vp, vp, fo, vp, vp, u32, C.POINTER(_Eval)]
+    L.ocffm_model_similar_items.argtypes = [vp, u64, vp, vp, vp, u32, u32, vp, vp]
+    L.ocffm_model_similar_to.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
+    L.ocffm_model_item_similarity.argtypes = [vp, u64, vp, vp, u32, vp]
     _lib = L
     return L
 
@@ -263,6 +269,13 @@ def _lists(candidates, rows: int):
     if cptr.size != rows + 1 or int(cptr.max()) > ccol.size:
         raise OcffmError(E_ARG, "candidates: cptr needs rows + 1 offsets into ccol")
     return cptr, (ccol if ccol.size else np.zeros(1, dtype=np.uint32))
+
+
+def _sim_flags(metric: str, keep_self: bool = False) -> int:
+    """The flags of the similarity entries (include/ocffm_similar.h)."""
+    if metric not in ("cosine", "dot"):
+        raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+    return (SIM_DOT if metric == "dot" else 0) | (SIM_KEEP_SELF if keep_self else 0)
 
 
 def _label_ranks(fn, among, h, X, seen, candidates):
@@ -980,6 +993,59 @@ class Model:
             return _evaluate(lambda h, x, sh, *a: L.ocffm_model_evaluate_fold(h, x, hist.h, C.byref(fo), sh, *a),
                              None, self.h, X, cuts, seen, None)
         return _evaluate(L.ocffm_model_evaluate, L.ocffm_model_evaluate_among, self.h, X, cuts, seen, candidates)
+
+    def similar_items(self, items, topn: int = 10, metric: str = "cosine", keep_self: bool = False, exclude=None):
+        """Top-``topn`` catalogue items by similarity to each catalogue item of
+        ``items`` (include/ocffm_similar.h ocffm_model_similar_items): cosine of
+        the items' cross-table embeddings, or their inner product with
+        ``metric="dot"``.  A query item is left out of its own row unless
+        ``keep_self``; ``exclude=(cptr, ccol)`` gives per-query lists of further
+        items to leave out.  ``(items uint32 [nq, topn], scores float64)`` as
+        ``recommend`` returns them."""
+        flags = _sim_flags(metric, keep_self)
+        q = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1)
+        xptr, xcol = (None, None) if exclude is None else _lists(exclude, q.size)
+        shape = (q.size, max(0, min(int(topn), REC_MAX_TOPN)))
+        out = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        pad = np.zeros(1, dtype=np.uint32)
+        _check(lib().ocffm_model_similar_items(self.h, q.size, _ptr(q if q.size else pad), _ptr(xptr), _ptr(xcol),
+                                               topn, flags, out.ctypes.data_as(C.c_void_p),
+                                               scores.ctypes.data_as(C.c_void_p)))
+        return out, scores
+
+    def similar_to(self, V: ImpData, topn: int = 10, row0: int = 0, rows: Optional[int] = None,
+                   metric: str = "cosine", exclude=None):
+        """The same for rows [row0, row0 + rows) of the item rows ``V`` (read
+        with ``item_Ds``), which need not be in the catalogue
+        (ocffm_model_similar_to); nothing is left out but the ``exclude``
+        lists."""
+        flags = _sim_flags(metric)
+        if rows is None:
+            rows = max(0, int(V.info["m"]) - row0)
+        xptr, xcol = (None, None) if exclude is None else _lists(exclude, rows)
+        shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
+        out = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        _check(lib().ocffm_model_similar_to(self.h, V.h, row0, rows, _ptr(xptr), _ptr(xcol), topn, flags,
+                                            out.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p)))
+        return out, scores
+
+    def item_similarity(self, a, b, metric: str = "cosine") -> np.ndarray:
+        """Similarity of the catalogue pairs ``(a[e], b[e])``
+        (ocffm_model_item_similarity): float64 [npairs], the values
+        ``similar_items`` returns bit for bit; ``-inf`` for an index outside the
+        catalogue."""
+        flags = _sim_flags(metric)
+        pa = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+        pb = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+        if pa.size != pb.size:
+            raise OcffmError(E_ARG, "item_similarity: a and b differ in length")
+        out = np.full(max(1, pa.size), -np.inf, dtype=np.float64)
+        pad = np.zeros(1, dtype=np.uint32)
+        _check(lib().ocffm_model_item_similarity(self.h, pa.size, _ptr(pa if pa.size else pad),
+                                                 _ptr(pb if pb.size else pad), flags, _ptr(out)))
+        return out[: pa.size]
 
     def counter(self, name: str) -> int:
         """Serving counter (include/ocffm.h ocffm_model_counter)."""
