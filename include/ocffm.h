@@ -810,6 +810,9 @@ int ocffm_model_counter(ocffm_model *m, const char *name, int64_t *value);
  * pair similarities, and queries by item rows that are not in the catalogue
  * are declared in ocffm_similar.h, included at the end of this header. */
 
+/* Diversified top-N (greedy MMR re-ranking of a row's pool by those
+ * similarities) is declared in ocffm_diverse.h, included after it. */
+
 /* Access.  ocffm_model_get_info fills Ds / used when the caller gave room;
  * ocffm_model_get_ds writes the f field sizes (user fields first).
  * ocffm_model_get copies to the host as fp64 like ocffm_problem_get: what 'W',
@@ -826,5 +829,6 @@ void ocffm_model_destroy(ocffm_model *m);
 
 #include "ocffm_fold.h"
 #include "ocffm_similar.h"
+#include "ocffm_diverse.h"
 
 #endif /* OCFFM_H */

@@ -1,7 +1,8 @@
 // model.hip — the stand-alone model handle (ocffm.h ocffm_model): W / H of a
 // saved or trained model, an item catalogue in the serving sweeps' form, and
-// the serving entries on it, the item-item similarities among them
-// (ocffm_similar.h, sim_kernels.hpp).  A third host of the serving driver
+// the serving entries on it, the item-item similarities (ocffm_similar.h,
+// sim_kernels.hpp) and the diversified top-N (ocffm_diverse.h,
+// mmr_kernels.hpp) among them.  A third host of the serving driver
 // (rank_driver.hpp) beside the Newton-CG problem (solver.hip) and the SGD
 // trainer (sgd.hip): the files are read on the host (model_file.cpp), any rows
 // are projected through W / H by one launch (k_project_side), and the sweeps,
@@ -24,6 +25,7 @@
 #include "fold_kernels.hpp"
 #include "kernels.hpp"
 #include "model_file.h"
+#include "mmr_kernels.hpp"
 #include "model_source.hpp"
 #include "rank_driver.hpp"
 #include "sim_kernels.hpp"
@@ -152,6 +154,9 @@ struct ModelBase {
                           uint32_t topn, uint32_t flags, uint32_t *items, double *scores) = 0;
   virtual void item_similarity(uint64_t npairs, const uint32_t *pa, const uint32_t *pb, uint32_t flags,
                                double *out) = 0;
+  virtual void recommend_diverse(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr,
+                                 const uint32_t *ccol, uint32_t topn, uint32_t pool, double theta, uint32_t flags,
+                                 uint32_t *items, double *scores, double *mmr, uint32_t *pos) = 0;
   virtual uint64_t get(char what, uint32_t b12, double *out, uint64_t cap) = 0;
   virtual void info(ocffm_model_info *out) const = 0;
   virtual const std::vector<uint64_t> &ds() const = 0;
@@ -495,6 +500,102 @@ template <typename real> class Model final : public ModelBase {
     const std::vector<double> kv = SimRank{*this, m}.score_pairs(L, krow, kitem, "similar");
     flush_prof();
     for (size_t t = 0; t < kv.size(); t++) out[where[t]] = kv[t];
+    end();
+  }
+
+  // -------------------------------------------------------- diversified
+  // Greedy MMR re-ranking of each row's top-`pool` list (ocffm_diverse.h):
+  // recommend's sweep (or recommend_among's list path when cptr is given) with
+  // topn = pool, and k_mmr as the driver's post-chunk hook on the chunk's
+  // device lists; only the rows x topn selection comes back.  Scratch is per
+  // chunk: chunk x topn results, and pool x pool similarities in LDS.
+  void recommend_diverse(const HostData &X, uint64_t row0, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol,
+                         uint32_t topn, uint32_t pool, double theta, uint32_t flags, uint32_t *items, double *scores,
+                         double *mmr, uint32_t *pos) override {
+    use_device();
+    need_items();
+    check_topn(X, row0, rows, topn, items);
+    if (pool < topn || pool > OCFFM_DIV_MAX_POOL) throw Error(OCFFM_E_ARG, "pool must be in topn..OCFFM_DIV_MAX_POOL");
+    if (!(theta >= 0.0 && theta <= 1.0)) throw Error(OCFFM_E_ARG, "theta must be in [0, 1]");
+    if (flags & ~OCFFM_REC_EXCLUDE_LABELS) throw Error(OCFFM_E_ARG, "unknown flag bits");
+    if (cptr) check_lists(cptr, ccol, rows);
+    else if (ccol) throw Error(OCFFM_E_ARG, "ccol without cptr");
+    check_rows(X, row0, rows);
+    if (rows == 0) return;
+    if (n_ == 0) {
+      none_lists(rows, topn, items, scores);
+      for (uint64_t e = 0; e < rows * topn; e++) {
+        if (mmr) mmr[e] = -std::numeric_limits<double>::infinity();
+        if (pos) pos[e] = OCFFM_REC_NONE;
+      }
+      return;
+    }
+    sim_norms();
+    begin();
+    const bool excl = (flags & OCFFM_REC_EXCLUDE_LABELS) && X.yptr.size() == X.m + 1 && !X.ycol.empty();
+    Query L;
+    query(L, X, row0, rows, excl ? &X : nullptr);
+    const RankModel<real> m = rank_model();
+    Rank dr{*this, m};
+    const uint64_t chunk = dr.chunk(rows);
+    DevBuf<uint32_t> dj, dp;
+    DevBuf<double> dv, dm;
+    dj.alloc(chunk * topn, false);
+    dp.alloc(chunk * topn, false);
+    dv.alloc(chunk * topn, false);
+    dm.alloc(chunk * topn, false);
+    MmrArgs<real> a{};
+    a.C = (int)C_;
+    a.pool = (int)pool;
+    a.topn = (int)topn;
+    a.ld = mmr_ld(pool);
+    a.Q = (const real *const *)qt_.p;
+    a.inv = siminv_.p;
+    a.w = 1.0 - theta;
+    a.theta = theta;
+    a.items = dj.p;
+    a.pos = dp.p;
+    a.scores = dv.p;
+    a.mmr = dm.p;
+    // LDS from the pool: a small pool keeps several workgroups per CU; above 64 KiB the kernel opts in
+    const size_t smem = mmr_lds_bytes<real>(pool);
+    if (smem > (64u << 10))
+      with_kp(kp_, [&](auto K) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mmr<real, decltype(K)::value>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      });
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> dev;
+    auto post = [&](uint64_t c0, uint64_t cr, const uint32_t *pj, const double *pv) {
+      hipEvent_t ea, eb;
+      HIPCHK(hipEventCreate(&ea));
+      HIPCHK(hipEventCreate(&eb));
+      dev.push_back({ea, eb});
+      a.R = cr;
+      a.pool_j = pj;
+      a.pool_v = pv;
+      HIPCHK(hipEventRecord(ea, stream_));
+      with_kp(kp_, [&](auto K) { launch(k_mmr<real, decltype(K)::value>, (unsigned)cr, BLOCK, smem, a); });
+      HIPCHK(hipEventRecord(eb, stream_));
+      const size_t o = c0 * topn, ne = cr * topn;
+      return std::vector<RankCopy>{{dj.p, items + o, ne * sizeof(uint32_t)},
+                                   {dv.p, scores ? scores + o : nullptr, ne * sizeof(double)},
+                                   {dm.p, mmr ? mmr + o : nullptr, ne * sizeof(double)},
+                                   {dp.p, pos ? pos + o : nullptr, ne * sizeof(uint32_t)}};
+    };
+    if (cptr)
+      dr.rerank(L, rows, cptr, ccol, pool, excl, nullptr, nullptr, "div_setup_us", "diverse", post);
+    else
+      dr.recommend(L, rows, pool, excl, nullptr, nullptr, "div_setup_us", "diverse",
+                   [](RecArgs<real> &, uint64_t, uint64_t) {}, post);
+    double dus = 0;  // (the driver has waited for the stream)
+    for (auto &e : dev) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+      dus += 1e3 * ms;
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    counters["div_kernel_us"] = (int64_t)dus;
     end();
   }
 
@@ -1259,6 +1360,13 @@ int ocffm_model_similar_to(ocffm_model *mod, const ocffm_data *Vq, uint64_t row0
 int ocffm_model_item_similarity(ocffm_model *mod, uint64_t npairs, const uint32_t *pa, const uint32_t *pb,
                                 uint32_t flags, double *out) {
   MODEL_CALL(mod->m->item_similarity(npairs, pa, pb, flags, out));
+}
+int ocffm_model_recommend_diverse(ocffm_model *mod, const ocffm_data *X, uint64_t row0, uint64_t rows,
+                                  const uint64_t *cptr, const uint32_t *ccol, uint32_t topn, uint32_t pool,
+                                  double theta, uint32_t flags, uint32_t *items, double *scores, double *mmr,
+                                  uint32_t *pos) {
+  MODEL_CALL(if (!X) throw Error(OCFFM_E_ARG, "null X");
+             mod->m->recommend_diverse(X->d, row0, rows, cptr, ccol, topn, pool, theta, flags, items, scores, mmr, pos));
 }
 int ocffm_model_counter(ocffm_model *mod, const char *name, int64_t *value) {
   MODEL_CALL(if (!name || !value) throw Error(OCFFM_E_ARG, "null argument");

@@ -21,6 +21,11 @@
 //   ocffm_model_similar_items; the query itself left out), the queries being
 //   the catalogue indices of the file, one per line, or every item for the
 //   word `all`; the output has --rec-out's format, one line per query.
+//   --diversify <theta> [--pool <n>]: --recommend's lists are re-ranked by
+//   greedy MMR over each row's top-n pool (ocffm_diverse.h
+//   ocffm_model_recommend_diverse; n defaults to min(128, 4 topn)); --rec-out
+//   keeps its format, item:score with the model score, in the order the items
+//   were taken.  With --rec-candidates and --rec-unseen; not with --fold-field.
 // item_file is the catalogue: any item rows in the model's item field space
 // (read with the model's item Ds, as a test file is with the train Ds).
 #include <chrono>
@@ -50,7 +55,10 @@ static std::string usage() {
          "--similar <path | all>: the --topn items most similar to each catalogue item of this file (one index per\n"
          "                        line), or to every item for the word all\n"
          "--sim-out <path>: where the similar items go (--rec-out's format, one line per query item)\n"
-         "--sim-metric cosine | dot: the similarity (default cosine)\n" +
+         "--sim-metric cosine | dot: the similarity (default cosine)\n"
+         "--diversify <theta>: re-rank --recommend's lists by greedy MMR, theta in [0, 1] the weight of the\n"
+         "                     similarity to the items already taken (0: no change)\n"
+         "--pool <n>: the MMR's pool, each row's top n, --topn..128 (default min(128, 4 topn))\n" +
          serve_usage("");
 }
 
@@ -83,7 +91,9 @@ int main(int argc, char **argv) {
   int precision = OCFFM_FP64, device = 0;
   bool binary = false;
   std::string pop_path, fold_hist, sim_path, sim_out, sim_metric = "cosine";
-  long fold_field = -1;
+  long fold_field = -1, pool = -1;
+  double theta = -1;
+  bool diversify = false;
   ocffm_param pd;
   ocffm_param_default(&pd);
   ocffm_fold fo{0, pd.omega, pd.lambda, pd.r};
@@ -112,6 +122,11 @@ int main(int argc, char **argv) {
       else if (a == "--similar") sim_path = value(false, "need a path or the word all after --similar");
       else if (a == "--sim-out") sim_out = value(false, "need to specify path after --sim-out");
       else if (a == "--sim-metric") sim_metric = value(false, "need cosine or dot after --sim-metric");
+      else if (a == "--diversify") {
+        theta = std::atof(value(true, "need theta after --diversify"));
+        diversify = true;
+      }
+      else if (a == "--pool") pool = std::atol(value(true, "need the pool size after --pool"));
       else if (so.take(a, value)) continue;
       else break;
     }
@@ -127,6 +142,15 @@ int main(int argc, char **argv) {
     if (!sim_path.empty() && sim_out.empty()) throw std::invalid_argument("--similar needs --sim-out <path>");
     if (sim_path.empty() && !sim_out.empty()) throw std::invalid_argument("--sim-out needs --similar <path | all>");
     if (sim_metric != "cosine" && sim_metric != "dot") throw std::invalid_argument("--sim-metric takes cosine or dot");
+    if (pool >= 0 && !diversify) throw std::invalid_argument("--pool needs --diversify <theta>");
+    if (diversify) {
+      if (so.rec_path.empty()) throw std::invalid_argument("--diversify needs --recommend <path>");
+      if (!(theta >= 0.0 && theta <= 1.0)) throw std::invalid_argument("--diversify takes theta in [0, 1]");
+      if (fold)
+        throw std::invalid_argument("--diversify cannot be combined with --fold-field: folded rows are not diversified");
+      if (pool < 0) pool = so.topn * 4 < OCFFM_DIV_MAX_POOL ? so.topn * 4 : OCFFM_DIV_MAX_POOL;
+      if (pool < so.topn || pool > OCFFM_DIV_MAX_POOL) throw std::invalid_argument("--pool must be in --topn..128");
+    }
     if (i + 1 >= argc) throw std::invalid_argument("model file and item file not specified");
     if (i + 2 < argc) throw std::invalid_argument(std::string("unexpected argument: ") + argv[i + 2]);
     const std::string model_path = argv[i], item_path = argv[i + 1];
@@ -175,7 +199,8 @@ int main(int argc, char **argv) {
     check(ocffm_model_set_items(mod, V));
     if (!pop.empty()) check(ocffm_model_set_popularity(mod, pop.data(), pop.size()));
     phase("items");
-    serve(ModelServer{mod, Hs, fo}, so, lists, ds.data(), mi.fu, phase);
+    serve(ModelServer{mod, Hs, fo, diversify ? theta : -1.0, (uint32_t)(diversify ? pool : 0)}, so, lists, ds.data(), mi.fu,
+          phase);
     if (!sim_path.empty()) {
       if (sim_path == "all") {
         ocffm_data_info vi;

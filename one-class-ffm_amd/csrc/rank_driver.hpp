@@ -119,6 +119,18 @@ struct RankPlan {
   uint64_t chunk, S, per;  // rows per launch; item slices; items per slice (multiple of REC_IT)
 };
 
+// The post-chunk hook of recommend / rerank: post(c0, cr, out_j, out_v) runs
+// inside the chunk's timed launches, after its last launch, with the chunk's
+// device lists (cr x topn items and scores, rows c0.. of the call); it adds its
+// own launches and returns the device-to-host copies that take the place of
+// copy_back (a null dst is skipped).  RankNoPost: no hook, copy_back as ever.
+struct RankCopy {
+  const void *src;
+  void *dst;
+  size_t bytes;
+};
+struct RankNoPost {};
+
 template <typename real, RecMode MODE, class Host> struct RankDriver {
   Host &h;
   const RankModel<real> &m;
@@ -201,6 +213,27 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
     h.sync();
   }
 
+  // A hook's copies (RankCopy) in copy_back's place
+  void copy_back(const std::vector<RankCopy> &cp) {
+    for (const RankCopy &c : cp)
+      if (c.dst && c.bytes) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, m.stream));
+    h.sync();
+  }
+  // The end of a chunk: the hook's launches (call this inside the timed body) ...
+  template <class Post>
+  std::vector<RankCopy> run_post(Post &&post, uint64_t c0, uint64_t cr, const DevBuf<uint32_t> &out_j,
+                                 const DevBuf<double> &out_v) {
+    if constexpr (std::is_same<std::decay_t<Post>, RankNoPost>::value) return {};
+    else return post(c0, cr, (const uint32_t *)out_j.p, (const double *)out_v.p);
+  }
+  // ... and the chunk's results to the host
+  template <class Post>
+  void finish_chunk(const std::vector<RankCopy> &cp, uint64_t c0, uint64_t cr, uint32_t topn,
+                    const DevBuf<uint32_t> &out_j, const DevBuf<double> &out_v, uint32_t *items, double *scores) {
+    if constexpr (std::is_same<std::decay_t<Post>, RankNoPost>::value) copy_back(c0, cr, topn, out_j, out_v, items, scores);
+    else copy_back(cp);
+  }
+
   // ---------------------------------------------------- recommendation
   // Top-N items of the rows of L.  The rows are scored in chunks: scratch is
   // chunk x slices x topn partial entries, never rows x n.
@@ -214,6 +247,12 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
   template <class Prep>
   void recommend(const RankRows<real> &L, uint64_t rows, uint32_t topn, bool excl, uint32_t *items, double *scores,
                  const char *setup_counter, const char *family, Prep &&prep) {
+    recommend(L, rows, topn, excl, items, scores, setup_counter, family, prep, RankNoPost{});
+  }
+  // post: the post-chunk hook (RankCopy above); items / scores are then unused
+  template <class Prep, class Post>
+  void recommend(const RankRows<real> &L, uint64_t rows, uint32_t topn, bool excl, uint32_t *items, double *scores,
+                 const char *setup_counter, const char *family, Prep &&prep, Post &&post) {
     const RankPlan pl = plan(rows, [](auto K) { return k_rec_topn<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = pl.chunk, S = pl.S;
     DevBuf<double> part_v, out_v;
@@ -234,6 +273,7 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
       const double depth = (double)m.C * m.kp;
       const double bytes = ((double)cr + (double)m.n) * depth * sizeof(real) + (double)m.n * sizeof(real) +
                            (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
+      std::vector<RankCopy> cp;
       h.prof_launch(family, bytes, [&] {
         prep(g, c0, cr);
         with_kp(m.kp, [&](auto K) {
@@ -242,8 +282,9 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
         });
         h.launch(k_rec_merge, (unsigned)cr, BLOCK, 0, cr, (int)S, (int)topn, (const double *)part_v.p,
                  (const uint32_t *)part_j.p, out_j.p, out_v.p);
+        cp = run_post(post, c0, cr, out_j, out_v);
       }, 2.0 * (double)cr * (double)m.n * depth);
-      copy_back(c0, cr, topn, out_j, out_v, items, scores);
+      finish_chunk<Post>(cp, c0, cr, topn, out_j, out_v, items, scores);
     }
     h.flush_prof();
   }
@@ -340,6 +381,12 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
   // chunk's work items x topn partial entries.
   void rerank(const RankRows<real> &L, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol, uint32_t topn,
               bool excl, uint32_t *items, double *scores, const char *setup_counter) {
+    rerank(L, rows, cptr, ccol, topn, excl, items, scores, setup_counter, "rerank", RankNoPost{});
+  }
+  // post: the post-chunk hook, as in recommend
+  template <class Post>
+  void rerank(const RankRows<real> &L, uint64_t rows, const uint64_t *cptr, const uint32_t *ccol, uint32_t topn,
+              bool excl, uint32_t *items, double *scores, const char *setup_counter, const char *family, Post &&post) {
     ListPlan p;
     plan_lists(p, rows, cptr, [](auto K) { return k_rerank<real, decltype(K)::value, MODE>; });
     const uint64_t chunk = p.chunk;
@@ -390,7 +437,8 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
       const double bytes = list_bytes(nc, cr, g.W) +
                            (double)g.W * 2.0 * topn * (sizeof(double) + sizeof(uint32_t)) +
                            (double)cr * topn * (sizeof(double) + sizeof(uint32_t));
-      h.prof_launch("rerank", bytes, [&] {
+      std::vector<RankCopy> cp;
+      h.prof_launch(family, bytes, [&] {
         if (g.W)
           with_kp(m.kp, [&](auto K) {
             constexpr int KP = decltype(K)::value;
@@ -398,8 +446,9 @@ template <typename real, RecMode MODE, class Host> struct RankDriver {
           });
         h.launch(k_rerank_merge, (unsigned)((cr + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, cr, c0, g.w0, (int)topn,
                  (const int64_t *)p.dwptr.p, (const double *)part_v.p, (const uint32_t *)part_j.p, out_j.p, out_v.p);
+        cp = run_post(post, c0, cr, out_j, out_v);
       }, 2.0 * (double)nc * depth);
-      copy_back(c0, cr, topn, out_j, out_v, items, scores);
+      finish_chunk<Post>(cp, c0, cr, topn, out_j, out_v, items, scores);
     }
     h.flush_prof();
   }

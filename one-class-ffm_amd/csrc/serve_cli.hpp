@@ -168,12 +168,20 @@ struct ModelServer {
   ocffm_model *h;
   const ocffm_data *hist = nullptr;  // predict --fold-history: the rows are folded in first
   ocffm_fold fo{};
+  double theta = -1;                 // predict --diversify: >= 0 re-ranks each row's top-`pool` list (ocffm_diverse.h)
+  uint32_t pool = 0;
   int recommend(const ocffm_data *X, std::uint64_t rows, uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+    if (theta >= 0)
+      return ocffm_model_recommend_diverse(h, X, 0, rows, nullptr, nullptr, topn, pool, theta, flags, items, scores,
+                                           nullptr, nullptr);
     if (hist) return ocffm_model_recommend_fold(h, X, hist, &fo, 0, rows, topn, flags, items, scores);
     return ocffm_model_recommend(h, X, 0, rows, topn, flags, items, scores);
   }
   int recommend_among(const ocffm_data *X, std::uint64_t rows, const std::uint64_t *cptr, const uint32_t *ccol,
                       uint32_t topn, uint32_t flags, uint32_t *items, double *scores) {
+    if (theta >= 0)
+      return ocffm_model_recommend_diverse(h, X, 0, rows, cptr, ccol, topn, pool, theta, flags, items, scores, nullptr,
+                                           nullptr);
     return ocffm_model_recommend_among(h, X, 0, rows, cptr, ccol, topn, flags, items, scores);
   }
   int evaluate(const ocffm_data *X, const ocffm_data *seen, const uint32_t *cuts, uint32_t ncut, ocffm_eval *out) {

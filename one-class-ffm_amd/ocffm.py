@@ -26,6 +26,7 @@ FP64, FP32 = 64, 32
 REC_MAX_TOPN, REC_EXCLUDE_LABELS, REC_NONE = 128, 1, 0xFFFFFFFF
 RANK_NONE, EVAL_MAX_CUTS = 0xFFFFFFFF, 8
 SIM_DOT, SIM_KEEP_SELF = 1, 2
+DIV_MAX_POOL = REC_MAX_TOPN
 COMM_ID_BYTES = 128
 
 
@@ -136,6 +137,8 @@ FOLD_EXPORTS = [
 ]
 # include/ocffm_similar.h (included by ocffm.h): items like this one, on a model
 SIMILAR_EXPORTS = ["ocffm_model_similar_items", "ocffm_model_similar_to", "ocffm_model_item_similarity"]
+# include/ocffm_diverse.h (included by ocffm.h): diversified top-N, on a model
+DIVERSE_EXPORTS = ["ocffm_model_recommend_diverse"]
 
 _lib = None
 
@@ -248,6 +251,7 @@ def lib():
     L.ocffm_model_similar_items.argtypes = [vp, u64, vp, vp, vp, u32, u32, vp, vp]
     L.ocffm_model_similar_to.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, vp, vp]
     L.ocffm_model_item_similarity.argtypes = [vp, u64, vp, vp, u32, vp]
+    L.ocffm_model_recommend_diverse.argtypes = [vp, vp, u64, u64, vp, vp, u32, u32, dbl, u32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1046,6 +1050,35 @@ class Model:
         _check(lib().ocffm_model_item_similarity(self.h, pa.size, _ptr(pa if pa.size else pad),
                                                  _ptr(pb if pb.size else pad), flags, _ptr(out)))
         return out[: pa.size]
+
+    def recommend_diverse(self, X: ImpData, topn: int = 10, theta: float = 0.3, pool: Optional[int] = None,
+                          exclude_labels: bool = False, row0: int = 0, rows: Optional[int] = None, candidates=None):
+        """Diversified top-``topn`` of rows [row0, row0 + rows) of ``X``
+        (include/ocffm_diverse.h ocffm_model_recommend_diverse): greedy MMR on
+        each row's top-``pool`` list (``recommend``'s, or with
+        ``candidates=(cptr, ccol)`` the one among the row's own list), trading
+        the normalised model score, weight ``1 - theta``, against the largest
+        cosine similarity to an item already taken, weight ``theta``.
+        ``pool=None`` means ``min(REC_MAX_TOPN, 4 * topn)``.  Returns ``(items
+        uint32 [rows, topn], scores float64, mmr float64, pos uint32)``: the
+        items in the order they were taken, their model scores, the value each
+        was taken at and its position in the pool; ``theta=0`` is ``recommend``."""
+        if rows is None:
+            rows = max(0, int(X.info["m"]) - row0)
+        if pool is None:
+            pool = min(REC_MAX_TOPN, 4 * int(topn))
+        shape = (rows, max(0, min(int(topn), REC_MAX_TOPN)))
+        items = np.full(shape, REC_NONE, dtype=np.uint32)
+        scores = np.full(shape, -np.inf, dtype=np.float64)
+        mmr = np.full(shape, -np.inf, dtype=np.float64)
+        pos = np.full(shape, REC_NONE, dtype=np.uint32)
+        flags = REC_EXCLUDE_LABELS if exclude_labels else 0
+        cptr, ccol = (None, None) if candidates is None else _lists(candidates, rows)
+        _check(lib().ocffm_model_recommend_diverse(self.h, X.h, row0, rows, _ptr(cptr), _ptr(ccol), topn, pool,
+                                                   float(theta), flags, items.ctypes.data_as(C.c_void_p),
+                                                   scores.ctypes.data_as(C.c_void_p), mmr.ctypes.data_as(C.c_void_p),
+                                                   pos.ctypes.data_as(C.c_void_p)))
+        return items, scores, mmr, pos
 
     def counter(self, name: str) -> int:
         """Serving counter (include/ocffm.h ocffm_model_counter)."""
